@@ -13,14 +13,24 @@ affine result on the host) over synthetic inputs that are ALREADY RESIDENT IN HB
 With N GPUs the job is ONE MSM sharded by points exactly like the reference's msm-level split
 (ec_multi_scalar_mul_parallel.nim:386-431); each step ends with an all_gather of one affine point per rank over RCCL and the
 host-side sum of the partials.  `--gpus N` with no size flag is the BASELINE metric: 2^20 pairs IN TOTAL (strong scaling,
-2^20 / N pairs per rank) as `value`, with the weak form (2^20 pairs per GPU) and, at N = 8, BASELINE configs[3] (2^24 pairs in
-total) timed in the same run and reported as extra keys of the same line.  --total-log2n T times 2^T pairs in total only,
+2^20 / N pairs per rank) as `value`; with --full the weak form (2^20 pairs per GPU) and, at N = 8, BASELINE configs[3] (2^24 pairs
+in total) are timed in the same run and reported as extra keys of the same line.  --total-log2n T times 2^T pairs in total only,
 --log2n L (with N > 1) 2^L pairs per GPU only (weak scaling).
 
-Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for every field).  Beside the pipelined `value` the line
-carries, at N = 1, `latency_ms_blocking` (median wall time of single blocking device-resident calls -- the reference
-bench's definition, one call per iteration, benchmarks/bench_ec_msm_bls12_381_g1.nim:43) and `hostptr_ms` (the same
-through the Constantine symbol on host pointers, PCIe included).
+Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for every field).  A plain run does only what `value` needs: it sets up,
+warms up, times the `--steps` MSMs and prints the line (`value`, `ms_per_step` = milliseconds of one timed step, the plan and the
+stage times of the timed loop).  Everything else is measured with `--full` only:
+    python bench.py --gpus 1 --steps 50 --warmup 5 --full
+adds, at N = 1, the roofline of the accumulate kernel (with a device-copy peak measured in the same run), `latency_ms_blocking`
+(median wall time of single blocking device-resident calls -- the reference bench's definition, one call per iteration,
+benchmarks/bench_ec_msm_bls12_381_g1.nim:43), `hostptr_ms` (the same through the Constantine symbol on host pointers, PCIe
+included), the cached-bases legs, the CPU baseline and the parity checks against the oracle; at N > 1 the other forms of the job
+(`strong_bound`, the weak form, configs[3], `hostptr_sharded_ms`).  --no-cpu-baseline / --no-latency leave legs of --full out.
+
+    python bench.py --gpus 1 --steps 50 --warmup 5 --dump-outputs bench_outputs
+writes the result of the last timed step -- the affine point a caller of the timed path receives, in the C-API byte layout
+(include/ctt_msm_hip.h: x then y, little-endian Montgomery limbs) -- as DIR/msm_result_affine.npy, float64 of shape
+(2, coordinate bytes), one byte per element.  The inputs are seeded: the same arguments give the same inputs on every run.
 """
 import argparse
 import collections
@@ -260,7 +270,13 @@ def main():
     ap.add_argument("--all-ranks-on-device", type=int, default=-1, help="testing: put every rank on this GPU")
     ap.add_argument("--cpu-only", action="store_true", help="BASELINE.json configs[0]: the CPU port against the big-integer oracle, "
                     "no GPU (use with --log2n 10)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline: roofline, blocking and "
+                    "host-pointer latency, cached bases, CPU baseline and parity (N = 1); the other forms of the job (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the result of the last timed step to "
+                    "DIR/msm_result_affine.npy (float64, one byte of the C-API affine point per element)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     explicit_log2n = args.log2n is not None
     if args.log2n is None:
         args.log2n = 20
@@ -433,12 +449,17 @@ def main():
                 "rccl_ranks_seen": ranks_seen(),
                 "workload": f"{curve} MSM, 2^{lg} pairs " + ("in total" if leg_strong else "per GPU") + f", {world} ranks, inputs resident in HBM, {leg['depth']} MSMs in flight"}
 
-    hbm_measured = measure_hbm_copy_peak(torch) if rank == 0 else None
+    hbm_measured = measure_hbm_copy_peak(torch) if rank == 0 and args.full else None
     lg = main_total_log2 if strong else args.log2n
     leg = timed_leg(strong, lg)
     n, first, total, dt, res, plan, stages = leg["n"], leg["first"], leg["total"], leg["dt"], leg["res"], leg["plan"], leg["stages"]
     scal, d_points, d_scal, ev_launches = leg["scal"], leg["d_points"], leg["d_scal"], leg["ev_launches"]
     value = total * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        # the last timed step's result as the caller receives it (N > 1: the sum of the partials, the same on every rank)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "msm_result_affine.npy"),
+                np.frombuffer(bytes(res), dtype=np.uint8).astype(np.float64).reshape(2, info.coord_bytes))
     label = BASELINE_CONFIG.get((curve, lg, world)) if not strong else ("configs[3]" if (curve, lg, world) == ("bls12_381_g1", 24, 8) else None)
     if strong and curve == "bls12_381_g1" and lg == 20:
         label = "the metric: 2^20 pairs at 1/2/4/8 GPUs"
@@ -450,8 +471,8 @@ def main():
                   + f"; pipelined throughput, {leg['depth']} MSMs in flight, inputs resident in HBM",
         "value": value,
         "value_kind": f"pipelined: steps / wall time with {leg['depth']} complete MSMs in flight (the host tail of MSM i runs under the GPU work of "
-                      "the following ones); `value_blocking` = N / latency of ONE blocking call (SURVEY 8d's definition, the reference bench's), "
-                      "`value_hostptr` = the same through the Constantine symbol on pageable host arrays (PCIe included)",
+                      "the following ones); with --full, `value_blocking` = N / latency of ONE blocking call (SURVEY 8d's definition, the reference "
+                      "bench's), `value_hostptr` = the same through the Constantine symbol on pageable host arrays (PCIe included)",
         "unit": "points/s",
         "n_gpus": world,
         "steps": args.steps,
@@ -482,7 +503,7 @@ def main():
         # ---- what bounds the split (same run, same boxes): (a) every rank its shard with no exchange and no barrier -- what the
         # all_gather of one point per rank and the host sum cost on top of the slowest rank's MSMs; (b) rank 0 alone on ALL the pairs --
         # the one-GPU figure the N-GPU line is a speed-up over (the other ranks wait at the barrier)
-        if strong:
+        if strong and args.full:
             own = timed_leg(True, lg, exchange=False)
             t = torch.tensor([own["dt"]], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -500,7 +521,7 @@ def main():
                 "note": "2^%d / %d pairs per rank: a small MSM is a chain of dependent launches (DESIGN.md section 5: 2.8 / 1.7 / 1.1 / 0.70 ms for "
                         "2^20 / 2^19 / 2^18 / 2^17 pairs on one GPU), so the split of a FIXED 2^20-pair job is bounded well below N x" % (lg, world)}
         # ---- the other forms of the same job, same run (driver form only: `--gpus N` with no size flag) --------------------------
-        if driver_form:
+        if driver_form and args.full:
             w = timed_leg(False, 20)
             out["weak_2pow20_per_gpu"] = leg_summary(w, False, 20)
             if world == 8 and curve == "bls12_381_g1":
@@ -510,7 +531,7 @@ def main():
         # ---- the in-library form: ONE process calls the Constantine symbol on host arrays, the library shards the call over the GPUs
         # (ctt_hip_msm_set_devices; what a Constantine caller on an 8-GPU node gets without a source change).  Rank 0 only, the other
         # ranks wait; PCIe included, never `value`.
-        if strong and not args.no_latency:
+        if strong and args.full and not args.no_latency:
             if rank == 0:
                 from constantine_amd import multiScalarMul_vartime, multiScalarMul_vartime_parallel
                 from constantine_amd.msm import set_devices
@@ -540,7 +561,7 @@ def main():
                                                      "(rank 0; the other ranks idle): the library's own sharding over the node's GPUs, PCIe included"}
             idle_barrier()
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel (bucket accumulation, k_accum); N > 1: rank 0's launches (every rank runs the same
         # kernel over its own shard) -----------------------------
         t_acc = stages.get("accumulate", 0.0) * 1e-3
@@ -587,7 +608,7 @@ def main():
             }
 
     # ---- the reference bench's own definition: one blocking call per iteration ----------------------------
-    if world == 1 and not args.no_latency:
+    if world == 1 and args.full and not args.no_latency:
         lat = []
         eng.enable_timings(False)   # the reference's bench times the bare call
         for _ in range(12):
@@ -625,7 +646,7 @@ def main():
     # Not `value`: the headline hands the points over per call, as the reference's bench does.  Here the bases are
     # prepared once (CachedBases(table=True): multiples 2^(c*w) * P of every base resident in HBM) and each step moves
     # nothing but works on the resident table.
-    if world == 1 and not args.no_latency and n <= (1 << 22):
+    if world == 1 and args.full and not args.no_latency and n <= (1 << 22):
         from constantine_amd.msm import CachedBases
         cb = {}
         for label, table in (("records", False), ("window_table", True)):
@@ -662,7 +683,7 @@ def main():
 
     if rank == 0:
         # ---- CPU baseline: the oracle port on the host cores, bounded sample; doubles as a parity check -----
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             from oracle import cref   # the checker: imported for this leg only
             m = min(n, 1 << args.cpu_sample_log2)
             budget = host_cpu_budget()           # the GPU box caps the container at a CPU quota

@@ -37,7 +37,7 @@ cp "$OUT/hbm_traffic_k_accum.json" profiles/hbm_traffic_k_accum.json
 [ "${ONLY:-}" = hbm ] && { cat "$OUT/hbm_traffic_k_accum.json"; exit 0; }
 
 # headline line, un-profiled
-timeout 600 python bench.py > "$OUT/bench_$TAG.json" 2> "$OUT/bench.err"
+timeout 600 python bench.py --full > "$OUT/bench_$TAG.json" 2> "$OUT/bench.err"
 
 # kernel trace + stats (rocpd database, summarised by tools/kernel_timeline.py)
 ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o p -- python "$REPO/bench.py" --steps 50 --warmup 5 \
@@ -76,12 +76,12 @@ done
 # the other BASELINE configs and the size sweep
 # (the lines of the other BASELINE configs keep their CPU / parity leg: `parity_vs_oracle_on_sample` and `parity_full_size_vs_discrete_logs`
 # are true / false in every configs[] line, not null -- round-5 review)
-timeout 400 python bench.py --curve bn254_snarks_g1 --log2n 22 --steps 20 --warmup 3 > "$OUT/bench_${TAG}_bn254_snarks_g1.json" 2>> "$OUT/bench.err"
-timeout 400 python bench.py --curve pallas --steps 20 --warmup 3 > "$OUT/bench_${TAG}_pallas.json" 2>> "$OUT/bench.err"
-timeout 400 python bench.py --curve vesta --steps 20 --warmup 3 > "$OUT/bench_${TAG}_vesta.json" 2>> "$OUT/bench.err"
-timeout 400 python bench.py --curve bls12_381_g2 --steps 20 --warmup 3 > "$OUT/bench_${TAG}_bls12_381_g2.json" 2>> "$OUT/bench.err"
+timeout 400 python bench.py --curve bn254_snarks_g1 --log2n 22 --steps 20 --warmup 3 --full > "$OUT/bench_${TAG}_bn254_snarks_g1.json" 2>> "$OUT/bench.err"
+timeout 400 python bench.py --curve pallas --steps 20 --warmup 3 --full > "$OUT/bench_${TAG}_pallas.json" 2>> "$OUT/bench.err"
+timeout 400 python bench.py --curve vesta --steps 20 --warmup 3 --full > "$OUT/bench_${TAG}_vesta.json" 2>> "$OUT/bench.err"
+timeout 400 python bench.py --curve bls12_381_g2 --steps 20 --warmup 3 --full > "$OUT/bench_${TAG}_bls12_381_g2.json" 2>> "$OUT/bench.err"
 for k in 16 17 18 19 22 24; do
-  timeout 300 python bench.py --log2n $k --steps 20 --warmup 3 --no-cpu-baseline > "$OUT/bench_${TAG}_bls12_381_g1_2pow$k.json" 2>> "$OUT/bench.err"
+  timeout 300 python bench.py --log2n $k --steps 20 --warmup 3 --no-cpu-baseline --full > "$OUT/bench_${TAG}_bls12_381_g1_2pow$k.json" 2>> "$OUT/bench.err"
 done
 timeout 300 python tools/bench_batch_ops.py > "$OUT/batch_ops_$TAG.txt" 2>> "$OUT/bench.err"
 timeout 300 python tools/bench_batch_ops_host.py > "$OUT/batch_affine_host_collection_$TAG.txt" 2>> "$OUT/bench.err"
@@ -108,9 +108,9 @@ timeout 300 python tools/bench_threads.py 16 40 > "$OUT/concurrent_callers_colle
   timeout 300 python tools/bench_table.py bls12_381_g2 18 0
 } 2>> "$OUT/bench.err" | grep '^{' > "$OUT/table_$TAG.jsonl"
 # the N-GPU line's code path end to end on this one GPU: two ranks sharing device 0 with a gloo exchange (a plumbing check, not a scaling point)
-timeout 300 python bench.py --gpus 2 --all-ranks-on-device 0 --backend gloo --steps 10 --warmup 2 > "$OUT/bench_${TAG}_2ranks_one_gpu_gloo.json" 2>> "$OUT/bench.err"
+timeout 300 python bench.py --gpus 2 --all-ranks-on-device 0 --backend gloo --steps 10 --warmup 2 --full > "$OUT/bench_${TAG}_2ranks_one_gpu_gloo.json" 2>> "$OUT/bench.err"
 # ... and the driver's 8-rank form with every leg of the line (strong 2^20, weak, configs[3] 2^24 in total, strong_bound, hostptr_sharded_ms over 8 contexts): plumbing only
-timeout 600 python bench.py --gpus 8 --all-ranks-on-device 0 --backend gloo --steps 3 --warmup 1 > "$OUT/bench_${TAG}_8ranks_one_gpu_gloo.json" 2>> "$OUT/bench.err"
+timeout 600 python bench.py --gpus 8 --all-ranks-on-device 0 --backend gloo --steps 3 --warmup 1 --full > "$OUT/bench_${TAG}_8ranks_one_gpu_gloo.json" 2>> "$OUT/bench.err"
 # same box, the previous round's library next to this one (tools/libctt_msm_hip_prev.so, built from the previous round's commit)
 if [ -f tools/libctt_msm_hip_prev.so ]; then
   { for a in "--log2n 16" "--log2n 17" "--log2n 18" "--log2n 19" "" "--curve bn254_snarks_g1 --log2n 20" "--curve bn254_snarks_g1 --log2n 22" "--curve pallas" "--curve bls12_381_g2 --log2n 18"; do

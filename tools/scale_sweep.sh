@@ -15,7 +15,7 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0
 NDEV=$(python -c 'import torch; print(torch.cuda.device_count())')
 for N in 1 2 4 8; do
   [ "$N" -le "$NDEV" ] || { echo "# $N GPUs: not on this node ($NDEV devices)"; continue; }
-  timeout 900 python bench.py --gpus $N --steps $STEPS --warmup $WARM --no-cpu-baseline --no-latency | tee "$OUT/weak_2pow20_n$N.json"
+  timeout 900 python bench.py --gpus $N --steps $STEPS --warmup $WARM --no-cpu-baseline --no-latency --full | tee "$OUT/weak_2pow20_n$N.json"
   timeout 900 python bench.py --gpus $N --total-log2n 20 --steps $STEPS --warmup $WARM --no-cpu-baseline --no-latency | tee "$OUT/strong_2pow20_n$N.json"
   timeout 900 python bench.py --gpus $N --total-log2n 24 --steps 6 --warmup 2 --no-cpu-baseline --no-latency | tee "$OUT/strong_2pow24_n$N.json"
 done
