@@ -6,7 +6,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CTT_MSM_HIP_LIB") or os.path.join(HERE, "libctt_msm_hip.so")
 
 _lib = None
-ABI_VERSION = 9  # ctt_hip_msm_abi_version() of the library this package was written against
+ABI_VERSION = 10  # ctt_hip_msm_abi_version() of the library this package was written against
 
 
 class HipLibraryMissing(RuntimeError):
@@ -70,6 +70,28 @@ def _share_hip_runtime_with_torch():
             ctypes.CDLL(cand, mode=ctypes.RTLD_GLOBAL)
         except OSError:
             pass
+
+
+_bw_lib = None
+
+
+def banderwagon_lib():
+    """libctt_msm_hip_banderwagon.so (include/ctt_msm_hip_banderwagon.h): the Banderwagon symbols under Constantine's names, over lib()."""
+    global _bw_lib
+    if _bw_lib is None:
+        lib()   # the engine first: the companion library resolves against the copy already loaded
+        path = os.path.join(HERE, "libctt_msm_hip_banderwagon.so")
+        if not os.path.exists(path):
+            raise HipLibraryMissing(f"{path} not found: build it with make -C constantine_amd/csrc")
+        L = ctypes.CDLL(path)
+        vp, sz = ctypes.c_void_p, ctypes.c_size_t
+        for coef in ("big", "fr"):
+            fn = getattr(L, f"ctt_banderwagon_ec_prj_multi_scalar_mul_{coef}_coefs_vartime")
+            fn.argtypes, fn.restype = [vp, vp, vp, sz], None
+            fn = getattr(L, f"ctt_hip_msm_banderwagon_ec_prj_{coef}")
+            fn.argtypes, fn.restype = [vp, vp, vp, sz], ctypes.c_int
+        _bw_lib = L
+    return _bw_lib
 
 
 def lib():

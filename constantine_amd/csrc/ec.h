@@ -14,10 +14,25 @@
 // bounded by multiples of p, tracked statically here in units of M = F::MULB (a product is < M*p):
 //     affine input x, y < M;   stored XYZZ:  X < 4M + 1 (xyzz_madd, see XYZZ_XB),  Y < 2M,  ZZ, ZZZ < M.
 // fsub<F,B>(a,b) = a - b + B*p needs b < B*p and yields bound(a)+B; the canonical field ignores B.
+//
+// The same bucket type also carries a second group law, selected by the coordinate field (IsEdwards below): twisted Edwards
+// a x^2 + y^2 = 1 + d x^2 y^2 in extended coordinates (X:Y:Z:T), x = X/Z, y = Y/Z, T = XY/Z -- Banderwagon (a = -5).  The
+// slots are x = X, y = Y, zz = Z, zzz = T, so that is_inf() (Z == 0) and inf() (all zero) keep their meaning: the pipeline zero-fills
+// buckets and heads, and an all-zero record is the neutral in memory; every Edwards formula turns it into a real point by a branch
+// where it reads an operand (the law itself would map (0:0:0:0) to itself forever).  The law's own neutral is (0:c:0:c).
+// The affine neutral is (0,1) and goes through the law like any point; (0,0) is not on the curve and never an input.
+// Completeness: a = -5 and d are both non-squares mod p, and the unified formulas fail only when a sum or difference reaches a
+// 2-torsion point at infinity, which the Banderwagon group (prime-order subgroup + (0,-1)) does not contain.  Inputs must be
+// valid Banderwagon elements, as in the reference (ec_twistededwards_projective.nim:196-300); other curve points give unspecified results.
 #pragma once
+#include <type_traits>
 #include "fpu.h"
 
 namespace ctt {
+
+// the twisted Edwards law applies to every field type over Banderwagon_Fp (Fp on the device, Fp64 on the host)
+template <class F> struct IsEdwards : std::false_type {};
+template <template <class> class FT> struct IsEdwards<FT<Banderwagon_Fp>> : std::true_type {};
 
 template <class F>
 struct Affine {
@@ -37,9 +52,74 @@ struct XYZZ {
   }
 };
 
+// --- twisted Edwards, extended coordinates (EFD twisted/extended; canonical field only) -----------------------------------
+template <class F>
+CTT_HD F ed_d() {   // d in Montgomery form, 32- or 64-bit limbs
+  F r;
+  constexpr int W = (int)(sizeof(r.l[0]) / 4);
+  for (int i = 0; i < F::N; i++) {
+    r.l[i] = BanderwagonCoef::D[W * i];
+    if constexpr (W == 2) r.l[i] |= (uint64_t)BanderwagonCoef::D[W * i + 1] << 32;
+  }
+  return r;
+}
+template <class F>
+CTT_HD F ed_mul_a(const F& v) { return F::neg(F::add(F::dbl(F::dbl(v)), v)); }   // a = -5
+// the tail shared by the additions (add-2008-hwcd): E, F = D - C, G = D + C, H = B - aA -> (EF, GH, FG, EH)
+template <class F>
+CTT_HD XYZZ<F> ed_add_tail(const F& A, const F& B, const F& C, const F& D, const F& E) {
+  const F Fv = F::sub(D, C), G = F::add(D, C), H = F::sub(B, ed_mul_a<F>(A));
+  return {F::mul(E, Fv), F::mul(G, H), F::mul(Fv, G), F::mul(E, H)};
+}
+// p + q, unified (add-2008-hwcd: 10M with the multiplication by d)
+template <class F>
+CTT_HD XYZZ<F> ed_add(const XYZZ<F>& p, const XYZZ<F>& q) {
+  if (q.is_inf()) return p;
+  if (p.is_inf()) return q;
+  const F A = F::mul(p.x, q.x), B = F::mul(p.y, q.y);
+  const F C = F::mul(F::mul(p.zzz, ed_d<F>()), q.zzz), D = F::mul(p.zz, q.zz);
+  const F E = F::sub(F::sub(F::mul(F::add(p.x, p.y), F::add(q.x, q.y)), A), B);
+  return ed_add_tail<F>(A, B, C, D, E);
+}
+// acc += (neg ? -q : q), q affine; -(x, y) = (-x, y).  madd-2008-hwcd with T2 = x*y computed here: 10M (the record holds x, y only)
+template <class F, class S>
+CTT_HD void ed_madd(XYZZ<F>& acc, bool& empty, const F& qx_in, const F& qy, S neg) {
+  const F qx = fcneg<F, 1>(qx_in, neg);
+  const F qt = F::mul(qx, qy);
+  if (empty) {
+    acc = {qx, qy, F::one(), qt};
+    empty = false;
+    return;
+  }
+  const F A = F::mul(acc.x, qx), B = F::mul(acc.y, qy), C = F::mul(F::mul(acc.zzz, ed_d<F>()), qt);
+  const F E = F::sub(F::sub(F::mul(F::add(acc.x, acc.y), F::add(qx, qy)), A), B);
+  acc = ed_add_tail<F>(A, B, C, acc.zz, E);
+}
+// 2p (dbl-2008-hwcd: 4M + 4S); Z = 1 for an affine point (mdbl)
+template <class F>
+CTT_HD XYZZ<F> ed_dbl_z(const F& X, const F& Y, const F& ZZ2) {   // ZZ2 = 2 Z^2
+  const F A = F::sqr(X), B = F::sqr(Y);
+  const F D = ed_mul_a<F>(A);
+  const F E = F::sub(F::sub(F::sqr(F::add(X, Y)), A), B);
+  const F G = F::add(D, B), Fv = F::sub(G, ZZ2), H = F::sub(D, B);
+  return {F::mul(E, Fv), F::mul(G, H), F::mul(Fv, G), F::mul(E, H)};
+}
+template <class F>
+CTT_HD XYZZ<F> ed_dbl(const XYZZ<F>& p) {
+  if (p.is_inf()) return p;
+  return ed_dbl_z<F>(p.x, p.y, F::dbl(F::sqr(p.zz)));
+}
+template <class F>
+CTT_HD Affine<F> ed_to_affine(const XYZZ<F>& p) {
+  if (p.is_inf()) return {F::zero(), F::one()};
+  const F i = F::inv(p.zz);
+  return {F::mul(p.x, i), F::mul(p.y, i)};
+}
+
 // 2*(x,y) for an affine, non-neutral point (x, y < M); y == 0 gives ZZ = 0, i.e. the neutral
 template <class F>
 CTT_HD XYZZ<F> xyzz_mdbl(const F& x, const F& y) {
+  if constexpr (IsEdwards<F>::value) return ed_dbl_z<F>(x, y, F::dbl(F::one()));
   constexpr int M = F::MULB;
   F U = F::dbl(y);                               // < 2M
   F V, xx, W, S;
@@ -56,6 +136,7 @@ CTT_HD XYZZ<F> xyzz_mdbl(const F& x, const F& y) {
 
 template <class F>
 CTT_HD XYZZ<F> xyzz_dbl(const XYZZ<F>& p) {
+  if constexpr (IsEdwards<F>::value) return ed_dbl<F>(p);
   constexpr int M = F::MULB;
   if (p.is_inf()) return p;
   F U = F::dbl(p.y);                             // < 4M
@@ -90,6 +171,7 @@ static constexpr int XYZZ_XB = 9;  // stored X < 9p (xyzz_madd's X3 = RR - PPP -
 // `neg`: bool, or SignMask (fpu.h) -- the sign as a lane mask word, negated in arithmetic instead of through v_cndmask_b32
 template <class F, class S = bool>
 CTT_HD void xyzz_madd_flag(XYZZ<F>& acc, bool& empty, const F& qx, const F& qy_in, S neg) {
+  if constexpr (IsEdwards<F>::value) return ed_madd<F, S>(acc, empty, qx, qy_in, neg);
   constexpr int M = F::MULB;                                  // a product is < M*p, M = 2
   constexpr bool L1 = LazyOps<F>::ONE, L2 = LazyOps<F>::BOTH;
   constexpr int XB = XYZZ_XB;
@@ -152,6 +234,7 @@ struct ZInRegs {
 };
 template <class F, class Z>
 CTT_HD void xyzz_madd_core(F& X, F& Y, Z& z, bool& empty, const F& qx, const F& qy_in, bool neg) {
+  static_assert(!IsEdwards<F>::value, "the holder form is for the quadratic-extension fields");
   constexpr int M = F::MULB;                                  // a product is < M*p, M = 2
   constexpr bool L1 = LazyOps<F>::ONE, L2 = LazyOps<F>::BOTH;
   constexpr int XB = XYZZ_XB;
@@ -220,6 +303,7 @@ CTT_HD void xyzz_madd(XYZZ<F>& acc, const Affine<F>& q, bool neg) {
 // ZZ, ZZZ < 2; out the same.  Lazy operands as in xyzz_madd_flag.
 template <class F>
 CTT_HD XYZZ<F> xyzz_add_inl(const XYZZ<F>& a, const XYZZ<F>& q) {
+  if constexpr (IsEdwards<F>::value) return ed_add<F>(a, q);
   constexpr int M = F::MULB;
   constexpr bool L1 = LazyOps<F>::ONE, L2 = LazyOps<F>::BOTH;
   constexpr int XB = XYZZ_XB;
@@ -256,6 +340,7 @@ CTT_HD_NOINLINE void xyzz_add(XYZZ<F>& acc, const XYZZ<F>& q) {
 // Canonical fields only (host tail, input generator).
 template <class F>
 CTT_HD Affine<F> xyzz_to_affine(const XYZZ<F>& p) {
+  if constexpr (IsEdwards<F>::value) return ed_to_affine<F>(p);
   if (p.is_inf()) return Affine<F>::inf();
   // one inversion: 1/(ZZ*ZZZ)
   F i = F::inv(F::mul(p.zz, p.zzz));

@@ -39,6 +39,10 @@ template <> CTT_HD Affine<VestaEc::F> generator<VestaEc>() {
   using F = VestaEc::F;
   return {gen_coord_fp<F, GenVesta>(0), gen_coord_fp<F, GenVesta>(1)};
 }
+template <> CTT_HD Affine<Banderwagon::F> generator<Banderwagon>() {
+  using F = Banderwagon::F;
+  return {gen_coord_fp<F, GenBanderwagon>(0), gen_coord_fp<F, GenBanderwagon>(1)};
+}
 template <> CTT_HD Affine<Bls12381G2::F> generator<Bls12381G2>() {
   using B = Bls12381G2::F::Base;
   using G = GenBls12381G2;

@@ -197,6 +197,15 @@ __device__ __forceinline__ F quad_bcast(const F& v) {
 
 template <class F>
 __device__ __forceinline__ void xyzz_add_quad(const XYZZ<F>* s1, const XYZZ<F>* s2, XYZZ<F>* d1, XYZZ<F>* d2, int role) {
+  if constexpr (IsEdwards<F>::value) {   // twisted Edwards: lane 0 of the quad adds alone (no quad form of that law yet)
+    if (role == 0) {
+      const XYZZ<F> x = *s1, y = *s2;
+      const XYZZ<F> r = xyzz_add_inl<F>(x, y);
+      *d1 = r;
+      if (d2) *d2 = r;
+    }
+    return;
+  }
   constexpr int M = F::MULB;
   const F* A = &s1->x;  // x, y, zz, zzz
   const F* Q = &s2->x;
@@ -260,6 +269,10 @@ __device__ __forceinline__ F quad_pick(int role, const F& a, const F& b, const F
 }
 template <class F>
 __device__ __forceinline__ void xyzz_dbl_quad_reg(XYZZ<F>& p, int role) {
+  if constexpr (IsEdwards<F>::value) {   // every lane of the quad holds the same copy
+    p = xyzz_dbl<F>(p);
+    return;
+  }
   constexpr int M = F::MULB;
   if (p.is_inf()) return;  // uniform inside the quad
   const F U = F::dbl(p.y);                                            // < 4M
@@ -280,6 +293,10 @@ __device__ __forceinline__ void xyzz_dbl_quad_reg(XYZZ<F>& p, int role) {
 // acc += q (q from memory), the accumulator in registers; same rounds as xyzz_add_quad
 template <class F>
 __device__ __forceinline__ void xyzz_add_quad_reg(XYZZ<F>& acc, const XYZZ<F>& q, int role) {
+  if constexpr (IsEdwards<F>::value) {
+    acc = xyzz_add_inl<F>(acc, q);
+    return;
+  }
   constexpr int M = F::MULB;
   if (q.is_inf()) return;
   if (acc.is_inf()) { acc = q; return; }

@@ -45,6 +45,11 @@ struct Bn254G1 { using F = Fp<BN254_Fp>; using FD = FpU<BN254_Fp_U>; using Fr = 
 struct Bn254G2 { using F = Fp2<Fp<BN254_Fp>>; using FD = F; using Fr = Fp<BN254_Fr>; static constexpr int BITS = 254; static constexpr int ID = 3; static constexpr double ACC_NS = 0.5, RED_NS = 1.2; static constexpr int NARROW_PRIO_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 0; };
 struct PallasEc { using F = Fp<Pallas_Fp>; using FD = FpU<Pallas_Fp_U>; using Fr = Fp<Vesta_Fp>; static constexpr int BITS = 255; static constexpr int ID = 4; static constexpr double ACC_NS = 0.056, RED_NS = 0.10; static constexpr int NARROW_PRIO_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 21; };
 struct VestaEc { using F = Fp<Vesta_Fp>; using FD = FpU<Vesta_Fp_U>; using Fr = Fp<Pallas_Fp>; static constexpr int BITS = 255; static constexpr int ID = 5; static constexpr double ACC_NS = 0.056, RED_NS = 0.10; static constexpr int NARROW_PRIO_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 21; };
+// Banderwagon: twisted Edwards (a = -5) over the BLS12-381 scalar field; ec.h selects the extended-coordinate law by the field type.
+// The device field is the saturated Fp (FD = F, as for BN254 G2): no carry-free set for this modulus yet, so there is no record
+// conversion and the mixed addition computes x*y itself (10M).  ACC_NS / RED_NS: ESTIMATES, not tuned -- about twice Pallas's figures
+// (saturated field, 10M against 8M+2S); DESIGN.md section 10 has the measured k_accum.
+struct Banderwagon { using F = Fp<Banderwagon_Fp>; using FD = F; using Fr = Fp<Banderwagon_Fr>; static constexpr int BITS = 253; static constexpr int ID = 6; static constexpr double ACC_NS = 0.12, RED_NS = 0.20; static constexpr int NARROW_PRIO_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 0; };
 
 // ---------------------------------------------------------------------------------------------
 // Booth signed digits

@@ -27,6 +27,8 @@ CURVES = {
     "bn254_snarks_g2": CurveInfo("bn254_snarks_g2", 3, "bn254_snarks_g2", 64, 254, False),
     "pallas": CurveInfo("pallas", 4, "pallas_ec", 32, 255, True),
     "vesta": CurveInfo("vesta", 5, "vesta_ec", 32, 255, True),
+    # twisted Edwards: projective / affine output only, Constantine-named symbols in libctt_msm_hip_banderwagon.so
+    "banderwagon": CurveInfo("banderwagon", 6, "banderwagon_ec", 32, 253, False),
 }
 
 OUT_AFF, OUT_JAC, OUT_PRJ = 0, 1, 2

@@ -40,10 +40,23 @@ def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _out_kind(info, coord):
+    """CTT_HIP_OUT_* of `coord`; Banderwagon (twisted Edwards) has no Jacobian coordinates"""
+    if coord not in _COORD or (coord == "jac" and info.cid == CURVES["banderwagon"].cid):
+        raise ValueError(f"no {coord!r} coordinates for {info.name}")
+    return _COORD[coord]
+
+
 def multiScalarMul_vartime(curve, coefs, points, coord="jac", fr_coefs=False):
     """r <- sum coefs[i]*points[i], via ctt_<curve>_<coord>_multi_scalar_mul_{big,fr}_coefs_vartime.
     Returns r as a uint8 array of 3 coordinates (X,Y,Z) in `coord` ("jac" or "prj")."""
     info, coefs, points = _check(curve, coefs, points)
+    if curve == "banderwagon":   # the companion library: projective only, the affine form is its Z = 1 representative
+        _out_kind(info, coord)
+        fn = getattr(_lib.banderwagon_lib(), f"ctt_banderwagon_ec_prj_multi_scalar_mul_{'fr' if fr_coefs else 'big'}_coefs_vartime")
+        r = np.zeros(info.jac_bytes, dtype=np.uint8)
+        fn(_ptr(r), _ptr(coefs), _ptr(points), coefs.shape[0])
+        return r[:info.aff_bytes].copy() if coord == "aff" else r
     L = _lib.lib()
     fn = getattr(L, f"ctt_{info.sym}_{coord}_multi_scalar_mul_{'fr' if fr_coefs else 'big'}_coefs_vartime")
     r = np.zeros(info.jac_bytes, dtype=np.uint8)
@@ -149,7 +162,7 @@ class DeviceMsm:
         nco = 2 if coord == "aff" else 3
         r = np.zeros(nco * info.coord_bytes, dtype=np.uint8)
         self._order(d_coefs, d_points)
-        rc = self.L.ctt_hip_msm_device(self.ctx, info.cid, COEF_FR if fr_coefs else COEF_BIG, _COORD[coord], _ptr(r),
+        rc = self.L.ctt_hip_msm_device(self.ctx, info.cid, COEF_FR if fr_coefs else COEF_BIG, _out_kind(info, coord), _ptr(r),
                                        self._dptr(d_coefs), self._dptr(d_points), n)
         if rc != 0:
             raise RuntimeError("ctt_hip_msm_device failed")
@@ -171,7 +184,7 @@ class DeviceMsm:
         info = CURVES[curve]
         nco = 2 if coord == "aff" else 3
         r = np.zeros(nco * info.coord_bytes, dtype=np.uint8)
-        if self.L.ctt_hip_msm_device_finish(self.ctx, t, _COORD[coord], _ptr(r)) != 0:
+        if self.L.ctt_hip_msm_device_finish(self.ctx, t, _out_kind(info, coord), _ptr(r)) != 0:
             raise RuntimeError("ctt_hip_msm_device_finish failed (ticket not outstanding)")
         return r
 
@@ -333,7 +346,7 @@ class CachedBases:
         curve, t = ticket
         nco = 2 if coord == "aff" else 3
         r = np.zeros(nco * self.info.coord_bytes, dtype=np.uint8)
-        if self.L.ctt_hip_msm_device_finish(self.ctx, t, _COORD[coord], _ptr(r)) != 0:
+        if self.L.ctt_hip_msm_device_finish(self.ctx, t, _out_kind(self.info, coord), _ptr(r)) != 0:
             raise RuntimeError("ctt_hip_msm_device_finish failed (ticket not outstanding)")
         return r
 
@@ -347,7 +360,7 @@ class CachedBases:
             raise AssertionError("more coefficients than cached bases")
         nco = 2 if coord == "aff" else 3
         r = np.zeros(nco * self.info.coord_bytes, dtype=np.uint8)
-        rc = self.L.ctt_hip_msm_with_bases(self.ctx, self.handle, COEF_FR if fr_coefs else COEF_BIG, _COORD[coord], _ptr(r),
+        rc = self.L.ctt_hip_msm_with_bases(self.ctx, self.handle, COEF_FR if fr_coefs else COEF_BIG, _out_kind(self.info, coord), _ptr(r),
                                            _ptr(coefs), coefs.shape[0], 0)
         if rc != 0:
             raise RuntimeError("ctt_hip_msm_with_bases failed")

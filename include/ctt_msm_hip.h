@@ -151,8 +151,11 @@ CTT_BATCH_AFFINE_DECL(vesta_ec_prj, vesta_ec_aff)
 int ctt_hip_last_error(void);
 const char* ctt_hip_last_error_message(void);   /* the same, in words; valid until the thread's next refused call */
 void ctt_hip_clear_last_error(void);
+/* CTT_HIP_BANDERWAGON (twisted Edwards; Constantine-named symbols in include/ctt_msm_hip_banderwagon.h): affine and projective
+ * output only (CTT_HIP_OUT_JAC is refused with -1), inputs must be valid Banderwagon elements; batch affine, subgroup check, field
+ * probe and KZG quotient refuse it with -1 */
 enum { CTT_HIP_BLS12_381_G1 = 0, CTT_HIP_BLS12_381_G2 = 1, CTT_HIP_BN254_SNARKS_G1 = 2,
-       CTT_HIP_BN254_SNARKS_G2 = 3, CTT_HIP_PALLAS = 4, CTT_HIP_VESTA = 5 };
+       CTT_HIP_BN254_SNARKS_G2 = 3, CTT_HIP_PALLAS = 4, CTT_HIP_VESTA = 5, CTT_HIP_BANDERWAGON = 6 };
 enum { CTT_HIP_COEF_BIG = 0, CTT_HIP_COEF_FR = 1 };
 enum { CTT_HIP_OUT_AFF = 0, CTT_HIP_OUT_JAC = 1, CTT_HIP_OUT_PRJ = 2 };
 int ctt_hip_msm_available(void);
