@@ -161,10 +161,11 @@ def _splitmix64(x):
     return z ^ (z >> 31)
 
 
-def synth_log(seed, j):
-    """discrete log of point j of ctt_hip_gen_points(seed, first = 0) to the base G"""
+def synth_log(seed, j, first=0):
+    """discrete log of point j of ctt_hip_gen_points(seed, first) to the base G"""
     m = (1 << 64) - 1
     sd = (seed ^ 0xA5A5A5A5A5A5A5A5) & m
+    j += first
     return (_splitmix64((sd + 4 * j) & m) | 1) | (_splitmix64((sd + 4 * j + 1) & m) << 64)
 
 

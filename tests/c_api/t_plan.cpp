@@ -10,7 +10,7 @@ int main() {
   const unsigned long long sizes[] = {1, 2, 5, 63, 64, 65, 1000, 4096, 16383, 16384, 16385, 65536, 1ull << 20, (1ull << 20) + 7,
                                       1ull << 22, 1ull << 24, 1ull << 26, (1ull << 26) + 1, 1ull << 27, 1ull << 28, 1ull << 29,
                                       1ull << 30, (1ull << 31) - 1};
-  for (int bits : {254, 255}) {
+  for (int bits : {253, 254, 255}) {
     for (unsigned long long n : sizes) {
       for (int c = 0; c <= 20; c++) {
         if (c == 1) continue;

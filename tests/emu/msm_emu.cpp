@@ -397,8 +397,15 @@ struct EmuCurve {
     for (uint32_t i = 0; i < n; i++) fr_quotient_out_body<Fr>(a, i);
   }
   static const EmuOps* ops() {
-    static const EmuOps o = {msm, msm_host, msm_table, gen, fop, fop_dev, dev_info, sum_reduce, batch_affine, msm_slots, fr_quotient};
-    return &o;
+    // twisted Edwards: no Jacobian / projective batch conversion and no KZG quotient, as the engine refuses them (is_weierstrass);
+    // the dispatcher answers -1 for an absent operation
+    if constexpr (IsEdwards<F>::value) {
+      static const EmuOps o = {msm, msm_host, msm_table, gen, fop, fop_dev, dev_info, sum_reduce, nullptr, msm_slots, nullptr};
+      return &o;
+    } else {
+      static const EmuOps o = {msm, msm_host, msm_table, gen, fop, fop_dev, dev_info, sum_reduce, batch_affine, msm_slots, fr_quotient};
+      return &o;
+    }
   }
 };
 
@@ -414,6 +421,8 @@ extern "C" const EmuOps* emu_ops_3() { return EmuCurve<Bn254G2>::ops(); }
 extern "C" const EmuOps* emu_ops_4() { return EmuCurve<PallasEc>::ops(); }
 #elif EMU_CURVE == 5
 extern "C" const EmuOps* emu_ops_5() { return EmuCurve<VestaEc>::ops(); }
+#elif EMU_CURVE == 6
+extern "C" const EmuOps* emu_ops_6() { return EmuCurve<Banderwagon>::ops(); }
 #endif
 
 #else  // dispatcher
@@ -425,6 +434,7 @@ const EmuOps* emu_ops_2();
 const EmuOps* emu_ops_3();
 const EmuOps* emu_ops_4();
 const EmuOps* emu_ops_5();
+const EmuOps* emu_ops_6();
 
 static const EmuOps* ops_of(int curve) {
   switch (curve) {
@@ -434,6 +444,7 @@ static const EmuOps* ops_of(int curve) {
     case 3: return emu_ops_3();
     case 4: return emu_ops_4();
     case 5: return emu_ops_5();
+    case 6: return emu_ops_6();
   }
   return nullptr;
 }
@@ -486,7 +497,7 @@ int emu_sum_reduce(int curve, int out_kind, void* r, const void* points, size_t 
 }
 int emu_batch_affine(int curve, int src_kind, void* dst, const void* src, size_t n, int K) {
   const EmuOps* o = ops_of(curve);
-  if (!o) return -1;
+  if (!o || !o->batch_affine) return -1;
   o->batch_affine(src_kind, dst, src, n, K);
   return 0;
 }
@@ -497,7 +508,7 @@ int emu_msm_slots(int curve, void* r3, const void* coefs, const void* points, si
 int emu_fr_quotient(int curve, const void* poly, const void* dom, const void* z_mont, const void* scale_mont, uint32_t n, uint32_t K,
                     void* q, void* y) {
   const EmuOps* o = ops_of(curve);
-  if (!o) return -1;
+  if (!o || !o->fr_quotient) return -1;
   o->fr_quotient(poly, dom, z_mont, scale_mont, n, K, q, y);
   return 0;
 }

@@ -215,3 +215,334 @@ def test_refusals(dev, torch_cuda):
         assert _prj(cb.msm(_big(ks), coord="prj")) == bw.msm_fast(ks, crs)
     finally:
         cb.close()
+
+
+# ----------------------------------------------------------------------------------------------
+# The layers the short-Weierstrass curves reach through tests/test_gpu_parity.py: explicit plans, skewed digits, host symbols
+# uploading in slices (k_accum<FD, INTO>: a code object of its own), sharding over contexts, window tables, ragged sizes, tickets.
+# Expected values: the points of gen_points are [s_i]G with s_i = bw.synth_log(seed, i), so the MSM is [sum k_i s_i mod r]G -- one
+# scalar multiplication of the Python oracle that does not depend on plan, slicing or sharding; bw.msm_fast where no logarithm is known.
+# ----------------------------------------------------------------------------------------------
+_LOGS = {}
+
+
+def _logs(seed, n):
+    have = _LOGS.get(seed, [])
+    if len(have) < n:
+        have = _LOGS[seed] = have + [bw.synth_log(seed, j) for j in range(len(have), n)]
+    return have[:n]
+
+
+def _rand_scalars(seed, n):
+    """(n, 32) bytes of uniform 253-bit scalars (about a quarter of them >= r)"""
+    sc = np.random.default_rng(seed).integers(0, 256, (n, 32), dtype=np.uint8)
+    sc[:, 31] &= 0x1F
+    return sc
+
+
+def _ints(sc):
+    return [int.from_bytes(row.tobytes(), "little") for row in sc]
+
+
+def _by_logs(sc, logs):
+    """[sum k_i s_i mod r]G for scalar bytes or integers"""
+    ks = _ints(sc) if isinstance(sc, np.ndarray) else sc
+    return bw.mul(sum(k * s for k, s in zip(ks, logs)) % bw.R, bw.G)
+
+
+def _neg_rows(pts):
+    """the affine records of -P for records of P: (x, y) -> (p - x, y), which is the same map on Montgomery residues"""
+    out = pts.copy()
+    for j in range(pts.shape[0]):
+        x = int.from_bytes(pts[j, :32].tobytes(), "little")
+        out[j, :32] = np.frombuffer(((bw.P - x) % bw.P).to_bytes(32, "little"), dtype=np.uint8)
+    return out
+
+
+def _set_default(key, value):
+    """an option of the default context, the one the host-pointer symbols and CachedBases(ctx=None) use"""
+    from constantine_amd import _lib
+    assert _lib.lib().ctt_hip_msm_set_option(None, key.encode(), int(value)) == 0
+
+
+def test_window_sizes_and_lane_spans(dev, torch_cuda):
+    """Same element for every plan: window bits (11 divides the scalar width 253: the extra top window), entries per lane, sort
+    slices; the first 50 scalars have their top bits on."""
+    n, seed = 5000, 91
+    d_pts = _synth(dev, torch_cuda, seed, n)
+    sc = _rand_scalars(92, n)
+    sc[:50, 24:31] = 0xFF
+    sc[:50, 31] = 0x1F
+    expect = _by_logs(sc, _logs(seed, n))
+    ds = _to_dev(torch_cuda, sc)
+    try:
+        for c, K, S in ((3, 4, 0), (5, 8, 64), (8, 16, 1000), (11, 0, 0), (11, 8, 64), (13, 0, 0), (15, 12, 3000), (16, 0, 0), (0, 0, 0)):
+            dev.set_option("c", c)
+            dev.set_option("K", K)
+            dev.set_option("S", S)
+            assert bw.aff_from(bytes(dev.msm("banderwagon", ds, d_pts, n, coord="aff"))) == expect, (c, K, S, dev.last_plan())
+    finally:
+        dev.set_option("c", 0)
+        dev.set_option("K", 0)
+        dev.set_option("S", 0)
+
+
+def test_horner_groups_and_merge_without_host_wait(dev, torch_cuda):
+    """The bit Horner of a window cut into groups of hb bits (one quad of lanes each -- for this curve lane 0 of the quad adds alone),
+    and the head merge deciding on the device how far its tree goes: same element for every group size, for uniform digits and for
+    the inputs whose head chains are far longer than the steps the plan enqueues (all scalars equal; a quarter of them equal)."""
+    n, seed = 60000, 191
+    d_pts = _synth(dev, torch_cuda, seed, n)
+    logs = _logs(seed, n)
+    sc = _rand_scalars(192, n)
+    sc_eq = np.tile(sc[:1], (n, 1))
+    sc_q = sc.copy()
+    sc_q[::4] = sc[1]
+    try:
+        for label, s in (("uniform", sc), ("all equal", sc_eq), ("quarter equal", sc_q)):
+            expect = _by_logs(s, logs)
+            ds = _to_dev(torch_cuda, s)
+            for c, hb, K in ((0, 0, 0), (13, 1, 0), (13, 3, 8), (16, 2, 0), (16, 15, 0), (9, 4, 4), (11, 8, 0), (15, 5, 12)):
+                dev.set_option("c", c)
+                dev.set_option("K", K)
+                dev.set_option("horner_bits", hb)
+                got = bw.aff_from(bytes(dev.msm("banderwagon", ds, d_pts, n, coord="aff")))
+                assert got == expect, (label, c, hb, K, dev.last_plan())
+        # more than 16 groups per window: the groups beyond a workgroup's 16 quads run in further blocks
+        expect = _by_logs(sc, logs)
+        ds = _to_dev(torch_cuda, sc)
+        for c, hb, hws in ((18, 1, 0), (19, 1, 0), (20, 1, 0), (20, 0, 1), (18, 0, 1), (20, 2, 0)):
+            dev.set_option("c", c)
+            dev.set_option("K", 0)
+            dev.set_option("horner_bits", hb)
+            dev.set_option("host_window_sums", hws)
+            got = bw.aff_from(bytes(dev.msm("banderwagon", ds, d_pts, n, coord="aff")))
+            assert got == expect, (c, hb, hws, dev.last_plan())
+    finally:
+        for k in ("c", "K", "horner_bits", "host_window_sums"):
+            dev.set_option(k, 0)
+
+
+def test_sort_under_skewed_digit_distributions(dev, torch_cuda):
+    """The two-pass bucket sort must not depend on the digits being uniform: giant buckets, groups several tiles long, medium
+    buckets straddling a tile end -- and the accumulation behind it sees buckets of a hundred thousand points of this law."""
+    n, seed = 1 << 18, 311
+    d_pts = _synth(dev, torch_cuda, seed, n)
+    logs = _logs(seed, n)
+    rng = np.random.default_rng(7)
+    uni = _rand_scalars(312, n)
+    cases = {"uniform": uni}
+    cases["five distinct scalars"] = uni[:5][rng.integers(0, 5, n)]
+    some = uni[:100]
+    cases["hundred distinct scalars"] = some[rng.integers(0, 100, n)]
+    low = uni.copy()
+    low[:, 1::2] &= 0x1F          # every 16-bit chunk < 2^13: three quarters of the bucket range stay empty
+    cases["low quarter of the bucket range"] = low
+    mix = uni.copy()
+    mix[: n // 2] = some[rng.integers(0, 100, n // 2)]
+    cases["half uniform, half repeated"] = mix
+    try:
+        for label, sc in cases.items():
+            sc = np.ascontiguousarray(sc)
+            expect = _by_logs(sc, logs)
+            ds = _to_dev(torch_cuda, sc)
+            for c in (0, 12):
+                dev.set_option("c", c)
+                assert bw.aff_from(bytes(dev.msm("banderwagon", ds, d_pts, n, coord="aff"))) == expect, (label, c)
+            for staged, xcd in ((0, 0), (0, 1), (2, 0), (2, 1)):
+                dev.set_option("sort_staged", staged)
+                dev.set_option("sort_xcd", xcd)
+                for c in (0, 13):
+                    dev.set_option("c", c)
+                    assert bw.aff_from(bytes(dev.msm("banderwagon", ds, d_pts, n, coord="aff"))) == expect, (label, c, staged, xcd)
+            dev.set_option("sort_staged", 1)
+            dev.set_option("sort_xcd", 1)
+    finally:
+        dev.set_option("c", 0)
+        dev.set_option("sort_staged", 1)
+        dev.set_option("sort_xcd", 1)
+
+
+def test_host_symbols_upload_in_slices(dev, torch_cuda):
+    """The host-pointer symbols upload the pairs in slices underneath the accumulation (MsmEngine::submit_host): ONE bucket set,
+    k_accum<FD, INTO> resumes from the stored sums -- for this curve by XYZZ::is_inf() on a record whose neutral, once a bucket has
+    cancelled, is (0 : c : c : 0) and not the all-zero one.  Same element for 1, 2, 3, 4, 8 slices and the automatic choice, through
+    the big- and the Fr-coefficient Constantine symbols; and an input whose second half cancels every bucket of the first."""
+    from constantine_amd import multiScalarMul_vartime
+    try:
+        for n in ((1 << 18) + 3, 40000):
+            seed = 600 + n
+            pts = _synth(dev, torch_cuda, seed, n).cpu().numpy()
+            logs = _logs(seed, n)
+            sc = _rand_scalars(601 + n, n)
+            ks = _ints(sc)
+            expect = _by_logs(ks, logs)
+            fr = _fr([k % bw.R for k in ks])
+            for chunks in ((0, 1, 2, 3, 4, 8) if n > 100000 else (0, 2, 3)):
+                _set_default("chunks", chunks)
+                assert _prj(multiScalarMul_vartime("banderwagon", sc, pts, coord="prj")) == expect, (n, chunks, "big")
+                assert _prj(multiScalarMul_vartime("banderwagon", fr, pts, coord="prj", fr_coefs=True)) == expect, (n, chunks, "fr")
+        # the second half is the first half with every point negated and the same scalars: whatever the first slices stored, the last
+        # ones cancel -- every bucket ends as the law's neutral, and so does the sum
+        h = (1 << 17) + 1
+        half = _synth(dev, torch_cuda, 77, h).cpu().numpy()
+        pts = np.concatenate([half, _neg_rows(half)])
+        sc = _rand_scalars(78, h)
+        sc = np.concatenate([sc, sc])
+        for chunks in (0, 1, 2, 3, 8):
+            _set_default("chunks", chunks)
+            r = multiScalarMul_vartime("banderwagon", sc, pts, coord="prj")
+            assert [bw.fp_from(bytes(r)[i:i + 32]) for i in (0, 32, 64)] == [0, 1, 1], chunks
+        # ... and a third part after the cancelled two: the buckets go on from the stored neutral
+        t = 50001
+        third = _synth(dev, torch_cuda, 79, t).cpu().numpy()
+        sc3 = _rand_scalars(80, t)
+        for chunks in (0, 3, 5):
+            _set_default("chunks", chunks)
+            r = multiScalarMul_vartime("banderwagon", np.concatenate([sc, sc3]), np.concatenate([pts, third]), coord="prj")
+            assert _prj(r) == _by_logs(sc3, _logs(79, t)), chunks
+    finally:
+        _set_default("chunks", 0)
+
+
+def test_host_symbols_shard_over_contexts(dev, torch_cuda):
+    """In-library sharding on one device: two (three) contexts on device 0, the symbols cut the call into balanced slices, one host
+    thread per context, and the partial results are added on the host (ec_sum_affine: the Edwards law there too)."""
+    from constantine_amd import multiScalarMul_vartime, set_devices, set_shard_min
+    try:
+        set_shard_min(1000)
+        for devices, n in (([0, 0], 70001), ([0, 0, 0], 70001), ([0, 0], 1500), ([0, 0, 0], 1500)):   # 1500 < 2 x shard_min: one context
+            set_devices(devices)
+            seed = 900 + n
+            pts = _synth(dev, torch_cuda, seed, n).cpu().numpy()
+            sc = _rand_scalars(901 + n, n)
+            ks = _ints(sc)
+            expect = _by_logs(ks, _logs(seed, n))
+            assert _prj(multiScalarMul_vartime("banderwagon", sc, pts, coord="prj")) == expect, (devices, n)
+            m = min(n, 4000)
+            got = multiScalarMul_vartime("banderwagon", _fr([k % bw.R for k in ks[:m]]), pts[:m], coord="aff", fr_coefs=True)
+            assert bw.aff_from(bytes(got)) == _by_logs(ks[:m], _logs(seed, m)), (devices, n, "fr")
+    finally:
+        set_devices([])
+        set_shard_min(1 << 15)
+
+
+@pytest.mark.parametrize("n", [16385, 40000, 100003, (1 << 20) + 7])
+def test_sizes_that_are_not_powers_of_two(dev, torch_cuda, n):
+    """Pair counts that are not powers of two (ragged last partition block, groups of uneven size), device-resident and over a
+    window table of the same points."""
+    from constantine_amd import CachedBases
+    seed = 411
+    d_pts = _synth(dev, torch_cuda, seed, n)
+    sc = _rand_scalars(412 + n, n)
+    expect = _by_logs(sc, _logs(seed, n))
+    ds = _to_dev(torch_cuda, sc)
+    assert bw.aff_from(bytes(dev.msm("banderwagon", ds, d_pts, n, coord="aff"))) == expect
+    cb = CachedBases("banderwagon", d_pts, ctx=dev.ctx, on_device=True, table=True)
+    try:
+        assert cb.window_bits > 0
+        assert _prj(cb.msm(ds, coord="prj")) == expect
+        assert _prj(cb.msm(sc, coord="prj")) == expect          # host-resident coefficients over the table
+    finally:
+        cb.close()
+
+
+def test_window_table_cached_bases(dev, torch_cuda):
+    """ctt_hip_msm_bases_create_table over 20000 bases: automatic and explicit window bits (5: many windows and long bucket chains;
+    11 divides the scalar width: the extra window), prefixes of the bases, a base (0, 1) -- which table_next_body doubles like any
+    point --, a repeated pair, both forms of the merged sort's second sweep, Fr Montgomery coefficients, all-zero scalars."""
+    from constantine_amd import CachedBases
+    n, seed = 20000, 911
+    pts = _synth(dev, torch_cuda, seed, n).cpu().numpy()
+    logs = list(_logs(seed, n))
+    pts[11], logs[11] = _pts([bw.O])[0], 0
+    pts[13], logs[13] = pts[12], logs[12]
+    for wb in (0, 5, 11, 15):
+        bases = CachedBases("banderwagon", pts, table=True, window_bits=wb)
+        try:
+            assert bases.window_bits == wb or (wb == 0 and bases.window_bits > 0)
+            for s, m in ((1, n), (3, n // 3), (4, 1)):
+                sc = _rand_scalars(s, m)
+                if m > 13:
+                    sc[13] = sc[12]
+                expect = _by_logs(sc, logs[:m])
+                assert _prj(bases.msm(sc, coord="prj")) == expect, (wb, m)
+                try:
+                    for staged in (0, 2):
+                        _set_default("sort_staged", staged)
+                        assert _prj(bases.msm(sc, coord="prj")) == expect, (wb, m, staged)
+                finally:
+                    _set_default("sort_staged", 1)
+            ks = _ints(_rand_scalars(5, n))
+            got = bases.msm(_fr([k % bw.R for k in ks]), coord="aff", fr_coefs=True)
+            assert bw.aff_from(bytes(got)) == _by_logs(ks, logs), wb
+            r = bases.msm(np.zeros((n, 32), np.uint8), coord="prj")
+            assert [bw.fp_from(bytes(r)[i:i + 32]) for i in (0, 32, 64)] == [0, 1, 1], wb
+        finally:
+            bases.close()
+
+
+def test_all_equal_points_and_all_equal_scalars(dev, torch_cuda):
+    """One point everywhere (every addition inside a bucket is P + P or kP + P: the unified law has to be right where the Weierstrass
+    one branches to its doubling), then one scalar everywhere too; and one scalar over distinct points (one bucket per window)."""
+    n = 22529
+    one = _synth(dev, torch_cuda, 51, 1)
+    d_pts = one.repeat(n, 1).contiguous()
+    log = bw.synth_log(51, 0)
+    sc = _rand_scalars(52, n)
+    got = dev.msm("banderwagon", _to_dev(torch_cuda, sc), d_pts, n, coord="aff")
+    assert bw.aff_from(bytes(got)) == bw.mul(sum(_ints(sc)) * log % bw.R, bw.G)
+    sc_eq = np.tile(sc[:1], (n, 1))
+    got = dev.msm("banderwagon", _to_dev(torch_cuda, sc_eq), d_pts, n, coord="aff")
+    assert bw.aff_from(bytes(got)) == bw.mul(_ints(sc[:1])[0] * n * log % bw.R, bw.G)
+    n = 20000
+    d_pts = _synth(dev, torch_cuda, 53, n)
+    sc_eq = np.tile(_rand_scalars(54, 1), (n, 1))
+    got = dev.msm("banderwagon", _to_dev(torch_cuda, sc_eq), d_pts, n, coord="aff")
+    assert bw.aff_from(bytes(got)) == _by_logs(sc_eq, _logs(53, n))
+
+
+def test_unknown_logs_at_size(dev, torch_cuda):
+    """Points nobody knows the logarithm of, 2^18 pairs: 1024 points of the Verkle CRS generator (past the 256 of the commitment),
+    tiled and permuted, with independent 253-bit scalars (a quarter of them >= r); the pairs of one point collapse to one scalar, so
+    the expected element is an MSM of 1024 pairs in the Python oracle.  The collapsed scalars are reduced mod 2r, not mod r: a
+    deserialised Banderwagon point is a subgroup point or one plus (0, -1), so its order divides 2r, and the comparison is of curve
+    points, not of classes modulo (0, -1).  Oracle side alone, measured on one CPU core:
+    9.2 s (bw.crs 5.8 s, bw.msm_fast 3.4 s)."""
+    from constantine_amd import multiScalarMul_vartime
+    m, n = 1024, 1 << 18
+    crs = bw.crs(m, skip=256)
+    owner = np.random.default_rng(4242).permutation(np.arange(n) % m)     # pair j carries point owner[j]
+    pts = _pts(crs)[owner]
+    sc = _rand_scalars(4243, n)
+    sums = [0] * m
+    for k, i in zip(_ints(sc), owner.tolist()):
+        sums[i] += k
+    expect = bw.msm_fast([s % (2 * bw.R) for s in sums], crs)
+    got = dev.msm("banderwagon", _to_dev(torch_cuda, sc), _to_dev(torch_cuda, pts), n, coord="aff")
+    assert bw.aff_from(bytes(got)) == expect
+    assert _prj(multiScalarMul_vartime("banderwagon", sc, pts, coord="prj")) == expect
+
+
+def test_three_banderwagon_tickets_in_flight(dev, torch_cuda):
+    """Three tickets of the curve outstanding together, finished out of order, sizes 3000, 70000 and 1: on plain device inputs and
+    on cached bases (a prefix of them per ticket)."""
+    from constantine_amd import CachedBases
+    sizes, seed = (3000, 70000, 1), 195
+    nmax = max(sizes)
+    d_pts = _synth(dev, torch_cuda, seed, nmax)
+    scs = [_rand_scalars(196 + i, m) for i, m in enumerate(sizes)]
+    dss = [_to_dev(torch_cuda, s) for s in scs]
+    expect = [_by_logs(s, _logs(seed, m)) for s, m in zip(scs, sizes)]
+    t = [dev.submit("banderwagon", dss[i], d_pts, sizes[i]) for i in range(3)]
+    assert bw.aff_from(bytes(dev.finish(t[2], coord="aff"))) == expect[2]
+    assert _prj(dev.finish(t[0], coord="prj")) == expect[0]
+    assert bw.aff_from(bytes(dev.finish(t[1], coord="aff"))) == expect[1]
+    cb = CachedBases("banderwagon", d_pts, ctx=dev.ctx, on_device=True)
+    try:
+        t = [cb.submit(dss[i], sizes[i]) for i in range(3)]
+        assert _prj(cb.finish(t[1], coord="prj")) == expect[1]
+        assert bw.aff_from(bytes(cb.finish(t[2], coord="aff"))) == expect[2]
+        assert _prj(cb.finish(t[0], coord="prj")) == expect[0]
+    finally:
+        cb.close()

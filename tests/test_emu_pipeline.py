@@ -416,12 +416,12 @@ def test_plan_fits_the_gpu_for_any_size():
     """The plan's roundings (msm_pipeline.h): the accumulate grid -- W rows of ceil(G/64) one-wave workgroups -- never exceeds
     the resident wave slots (one workgroup more means a second round of a single wave: measured +28 % on BN254 2^22 at c = 15),
     the partition blocks are at most 512 (2048 from 2^23 pairs on) + a rounding remainder and all of one size, every entry has a lane; for sizes that are
-    and are not powers of two, both scalar widths, both occupancies, and the window-table form."""
+    and are not powers of two, the three scalar widths (253: Banderwagon), both occupancies, and the window-table form."""
     rng = random.Random(99)
     sizes = [1, 2, 63, 64, 65, 1000, 4096, 65536, 65537, 100000, (1 << 17) + 777, 3 << 16, 1000003, 1 << 20, (1 << 20) + 12345,
              (1 << 22) + 77777, 1 << 24, (1 << 24) + 1, 5 << 22] + [rng.randrange(1, 1 << 25) for _ in range(200)]
     for n in sizes:
-        for bits, lanes in ((255, 131072), (254, 262144), (255, 65536)):
+        for bits, lanes in ((255, 131072), (254, 262144), (255, 65536), (253, 131072), (253, 262144)):
             p = emu.plan(n, bits, lanes)
             # balanced windows over bits + 1 bits: r of cb + 1 bits, the others cb; c is the widest
             assert p["cb"] * p["W"] + p["r"] == bits + 1 and 0 <= p["r"] < p["W"] and p["c"] == p["cb"] + (1 if p["r"] else 0)
