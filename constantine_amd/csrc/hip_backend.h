@@ -477,6 +477,56 @@ __global__ void k_field_op(int op, const F* a, const F* b, F* r, uint32_t n) {
   r[j] = o;
 }
 
+// probe of the group law (msm_bodies.h ec_probe): raw XYZZ<FD> records in; out, per result record, the record and one flag word
+// (is_inf() of the result as the code sees it)
+template <class FD>
+struct EcProbeOut {
+  XYZZ<FD> r;
+  uint32_t inf;
+};
+template <class FD>
+__global__ void __launch_bounds__(EC_BLOCK) k_ec_probe(int op, const XYZZ<FD>* a, const XYZZ<FD>* b, EcProbeOut<FD>* out, uint32_t n) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const XYZZ<FD> x = a[j], y = b[j];
+  XYZZ<FD> r;
+  const uint32_t inf = ec_probe<FD>(op, x, y, r);
+  out[j].r = r;
+  out[j].inf = inf;
+}
+// the four-lane forms, one quad per element:  16 xyzz_add_quad with d2 (two records per element: d1, d2)   17 the same with
+// d2 = nullptr (one record)   18 xyzz_add_quad_reg   19 xyzz_dbl_quad_reg (four records per element: every lane's copy)
+template <class FD>
+__global__ void __launch_bounds__(EC_BLOCK) k_ec_probe_quad(int op, const XYZZ<FD>* a, const XYZZ<FD>* b, EcProbeOut<FD>* out, uint32_t n) {
+  const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t j = lane >> 2;
+  const int role = (int)(lane & 3u);
+  if (j >= n) return;   // (whole quads leave together)
+  if (op == EC_PROBE_QUAD) {
+    xyzz_add_quad<FD>(a + j, b + j, &out[2 * (size_t)j].r, &out[2 * (size_t)j + 1].r, role);
+  } else if (op == EC_PROBE_QUAD + 1) {
+    xyzz_add_quad<FD>(a + j, b + j, &out[j].r, (XYZZ<FD>*)nullptr, role);
+  } else {
+    XYZZ<FD> acc = a[j];
+    if (op == EC_PROBE_QUAD + 2) {
+      const XYZZ<FD> q = b[j];
+      xyzz_add_quad_reg<FD>(acc, q, role);
+    } else {
+      xyzz_dbl_quad_reg<FD>(acc, role);
+    }
+    out[4 * (size_t)j + role].r = acc;
+    out[4 * (size_t)j + role].inf = acc.is_inf() ? 1u : 0u;
+  }
+}
+// flag words of the memory forms (several lanes write one record there): a launch of its own, after the records are complete
+template <class FD>
+__global__ void __launch_bounds__(EC_BLOCK) k_ec_probe_flags(EcProbeOut<FD>* out, uint32_t n) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const XYZZ<FD> r = out[j].r;
+  out[j].inf = r.is_inf() ? 1u : 0u;
+}
+
 // ---------------------------------------------------------------------------------------------
 // HIP backend
 // ---------------------------------------------------------------------------------------------
@@ -871,6 +921,7 @@ struct CurveOps {
   // underneath the accumulation like the pairs of submit_host (MsmEngine::submit_host with d_prepared)
   int (*submit_host_bases)(void* eng, const MsmOptions* opt, const void* h_coefs, int coef_is_fr, const void* d_prepared, uint32_t n,
                            int table_c, uint32_t table_n, void* d_stage_coefs, int chunks, int* plan);
+  bool (*ec_probe_has)(int op);   // group-law probe ops (field_op with 32 + op) this curve serves
 };
 
 template <class C>
@@ -954,7 +1005,31 @@ struct CurveImpl {
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(bk->stream));
   }
+  static bool probe_has(int op) { return ec_probe_has<FD>(op); }
   static void field_op(HipBackend* bk, int op, const void* d_a, const void* d_b, void* d_r, uint32_t n) {
+    if (op >= 32) {  // group-law probe over raw XYZZ<FD> records (the caller has checked ec_probe_has)
+      const int eop = op - 32;
+      using Rec = XYZZ<FD>;
+      using Out = EcProbeOut<FD>;
+      if (n == 0) return;
+      if (eop < EC_PROBE_QUAD) {
+        hipLaunchKernelGGL(k_ec_probe<FD>, dim3((n + EC_BLOCK - 1) / EC_BLOCK), dim3(EC_BLOCK), 0, bk->stream, eop, (const Rec*)d_a,
+                           (const Rec*)d_b, (Out*)d_r, n);
+        HIP_CHECK(hipGetLastError());
+      } else {
+        const uint32_t lanes = 4u * n;
+        hipLaunchKernelGGL(k_ec_probe_quad<FD>, dim3((lanes + EC_BLOCK - 1) / EC_BLOCK), dim3(EC_BLOCK), 0, bk->stream, eop,
+                           (const Rec*)d_a, (const Rec*)d_b, (Out*)d_r, n);
+        HIP_CHECK(hipGetLastError());
+        if (eop < EC_PROBE_QUAD + 2) {
+          const uint32_t recs = eop == EC_PROBE_QUAD ? 2u * n : n;
+          hipLaunchKernelGGL(k_ec_probe_flags<FD>, dim3((recs + EC_BLOCK - 1) / EC_BLOCK), dim3(EC_BLOCK), 0, bk->stream, (Out*)d_r, recs);
+          HIP_CHECK(hipGetLastError());
+        }
+      }
+      HIP_CHECK(hipStreamSynchronize(bk->stream));
+      return;
+    }
     if (op >= 16) {  // device-field probe (raw FD limbs out); only meaningful when FD != F
       hipLaunchKernelGGL((k_field_op_dev<F, FD>), dim3((n + 255) / 256), dim3(256), 0, bk->stream, op - 16, (const F*)d_a,
                          (const F*)d_b, (FD*)d_r, n);
@@ -1043,7 +1118,7 @@ struct CurveImpl {
     return 0;
   }
   static const CurveOps* ops() {
-    static const CurveOps o = {C::ID, sizeof(Affine<F>), create, destroy, submit, finish, submit_host, bases_prepare, submit_bases, gen_points, field_op, ec_sum_affine, sum_reduce, batch_affine, sizeof(F), subgroup_check, table_prepare, fr_quotient, sizeof(typename C::Fr), subgroup_check_host, submit_host_bases};
+    static const CurveOps o = {C::ID, sizeof(Affine<F>), create, destroy, submit, finish, submit_host, bases_prepare, submit_bases, gen_points, field_op, ec_sum_affine, sum_reduce, batch_affine, sizeof(F), subgroup_check, table_prepare, fr_quotient, sizeof(typename C::Fr), subgroup_check_host, submit_host_bases, probe_has};
     return &o;
   }
 };

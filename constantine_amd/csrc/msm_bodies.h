@@ -957,6 +957,52 @@ CTT_HD FD dev_field_probe(int op, const FD& x, const FD& y) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Probe of the group law over the device field FD for the unit tests (GPU: k_ec_probe, CPU: tests/emu).  Operands are raw
+// records XYZZ<FD>, so the caller chooses the representative of every coordinate (x~ + k*p); the mixed forms take x, y of b.
+// Every op calls the instantiation the pipeline uses:
+//   0 .. 3    xyzz_madd_flag<FD, SignMask>(a, empty, b.x, b.y, sign)   bit 0 = sign (1: subtract), bit 1 = empty
+//   4 .. 7    xyzz_madd_core<FD, ZInRegs<FD>>, the same bits           (short Weierstrass only)
+//   8         xyzz_add_inl(a, b)       9  xyzz_dbl(a)       10  xyzz_mdbl(a.x, a.y)
+// (16 .. 19 are the four-lane forms of hip_backend.h, GPU only.)  The mixed forms report their `empty` flag and write the
+// all-zero record with it, as every caller of theirs does; the other ops report is_inf() of the result.
+// ---------------------------------------------------------------------------------------------
+static constexpr int EC_PROBE_QUAD = 16;   // first four-lane op
+static constexpr int EC_PROBE_END = 20;
+template <class FD>
+CTT_HD uint32_t ec_probe(int op, const XYZZ<FD>& a, const XYZZ<FD>& b, XYZZ<FD>& r) {
+  if (op < 8) {
+    XYZZ<FD> acc = a;
+    bool empty = (op & 2) != 0;
+    const uint32_t sign = (uint32_t)(op & 1);
+    if (op < 4) {
+      xyzz_madd_flag<FD, SignMask>(acc, empty, b.x, b.y, SignMask(sign << 31));
+    } else {
+      if constexpr (!IsEdwards<FD>::value) {
+        ZInRegs<FD> z;
+        z.put(acc.zz, acc.zzz);
+        xyzz_madd_core<FD, ZInRegs<FD>>(acc.x, acc.y, z, empty, b.x, b.y, sign != 0u);
+        z.get(acc.zz, acc.zzz);
+      }
+    }
+    r = empty ? XYZZ<FD>::inf() : acc;
+    return empty ? 1u : 0u;
+  }
+  switch (op) {
+    case 8: r = xyzz_add_inl<FD>(a, b); break;
+    case 9: r = xyzz_dbl<FD>(a); break;
+    default: r = xyzz_mdbl<FD>(a.x, a.y); break;
+  }
+  return r.is_inf() ? 1u : 0u;
+}
+// which ops a curve's coordinate field serves (the holder form does not exist for the twisted Edwards law)
+template <class FD>
+CTT_HD bool ec_probe_has(int op) {
+  if (op < 0 || op >= EC_PROBE_END || (op > 10 && op < EC_PROBE_QUAD)) return false;
+  if (IsEdwards<FD>::value && op >= 4 && op < 8) return false;
+  return true;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Subgroup check of many points at once: ok[j] = (P_j has order r), r = the curve order (the modulus of C::Fr) -- [r]P_j = neutral.
 // What the reference's deserialisers do per point (e.g. ethereum_evm_precompiles.nim fromRawCoords -> isInSubgroup); here the
 // MSM's callers (EIP-2537 G1MSM/G2MSM, KZG commitments) validate all their points with one launch: the bits of r are the same

@@ -125,8 +125,9 @@ class DeviceMsm:
             self.ctx = None
 
     def set_option(self, key, value):
-        """ctt_hip_msm_set_option: "c", "K", "S", "chunks", "horner_bits", "host_window_sums", "sort_staged", "sort_xcd", "timings", "timings_every"
-        (include/ctt_msm_hip.h); 0 = automatic / off.  KeyError for an unknown key."""
+        """ctt_hip_msm_set_option: "c", "K", "S", "chunks", "horner_bits", "host_window_sums", "sort_staged", "sort_xcd", "timings", "timings_every",
+        and the forms of the head merge and the stream placements of a pipelined MSM: "merge_chain", "merge_lmax", "merge_queue_quad",
+        "early_tail" (default 1), "front_side", "pyr0_tail" (include/ctt_msm_hip.h); 0 = automatic / off.  KeyError for an unknown key."""
         if self.L.ctt_hip_msm_set_option(self.ctx, key.encode(), int(value)) != 0:
             raise KeyError(key)
 

@@ -187,6 +187,13 @@ void ctt_hip_msm_ctx_destroy(ctt_hip_msm_ctx* ctx);
  * "host_window_sums" (legacy spelling: 1 = groups of one bit, 2 = one group per window), "timings" 1 = record the
  * stage events ctt_hip_msm_last_timings reads (2 = the accumulate stage and the total only), "timings_every" k = only every
  * k-th MSM records them (the others report zeros; default 1).  value 0 = automatic / off.  Returns 0, or -1 for an unknown key.
+ * Forms the plan otherwise chooses by itself (tests and experiments): "merge_chain" head merge 1 = the queue form always, 2 = the tree
+ * always; "merge_lmax" longest chain of heads the queue form walks with one quad (0 = 8; longer chains go to one workgroup per
+ * window); "merge_queue_quad" 2 = the queue kernel with one lane per chain instead of four; "early_tail" merge and every reduction
+ * pass of a pipelined MSM on the tail stream (0 never, 1 automatic -- the default --, 2 whenever pipelining); "front_side"
+ * conversion and sort of a pipelined MSM on the front stream (1 whenever pipelining, 2 never); "pyr0_tail" 1 = the first reduction
+ * pass of a small MSM on the tail stream.  A context also reads $CTT_HIP_MSM_MERGE_CHAIN, $CTT_HIP_MSM_MERGE_LMAX and
+ * $CTT_HIP_MSM_QUAD (reduction passes of at most this many additions run with four lanes per addition) when it is created.
  * A context created with $CTT_HIP_CU_TAIL = r > 0 partitions the chip: its tail stream runs on r compute units of every XCD
  * (hipExtStreamCreateWithCUMask), its main stream on the others -- an experiment of round 6, measured slower than sharing the chip
  * (profiles/cu_mask_r06.txt); such streams are BLOCKING streams: do not order them behind the legacy null stream. */
@@ -253,7 +260,16 @@ int ctt_hip_msm_last_timings(ctt_hip_msm_ctx* ctx, float* ms, int cap);
 int ctt_hip_msm_last_plan(ctt_hip_msm_ctx* ctx, int* out, int cap);
 /* d_out[i] = [s_i]G, deterministic synthetic subgroup points (bench / test inputs) */
 int ctt_hip_gen_points(ctt_hip_msm_ctx* ctx, int curve, uint64_t seed, uint64_t first, uint32_t n, void* d_out);
-/* element-wise coordinate-field op on device arrays (0 mul, 1 sqr, 2 add, 3 sub, 4 neg): kernel unit tests */
+/* kernel unit tests on device arrays.  op 0 .. 4: element-wise coordinate-field op (0 mul, 1 sqr, 2 add, 3 sub, 4 neg), operands
+ * and result in the C-API representation; 16 .. 23: the same operands through the device field, raw device limbs out (curves that
+ * compute in the carry-free field).  Both refused (-1) for Banderwagon.
+ * op 32 + k: the group law, every curve.  d_a, d_b: n raw device records (X, Y, ZZ, ZZZ; for Banderwagon X, Y, Z, T), 32-bit words in
+ * the device representation of the coordinate field -- the caller chooses the representative of every coordinate.  d_r: per result
+ * record, the record followed by one flag word (1 = the code takes it for the neutral element).  k = 0 .. 3 the mixed addition of the
+ * accumulate kernel, a += +-(b.x, b.y) (bit 0: subtract, bit 1: a is empty); 4 .. 7 the same in its X, Y + ZZ/ZZZ-holder form (not
+ * Banderwagon); 8 a + b; 9 2a; 10 2(a.x, a.y) -- one result record per element.  Four lanes per element: 16 the memory form with both
+ * destinations (two records per element), 17 with one (one record), 18 the register form of a + b, 19 of 2a (four records per
+ * element: every lane's copy).  -1 for an op the curve does not have. */
 int ctt_hip_field_op(ctt_hip_msm_ctx* ctx, int curve, int op, const void* d_a, const void* d_b, void* d_r, uint32_t n);
 /* host-only: r (`out_kind` layout) = sum of n affine points -- combines the per-GPU partial results of a
  * sharded MSM (the `r ~+= partial` of ec_multi_scalar_mul_parallel.nim:427-429). Needs no GPU. */

@@ -37,6 +37,7 @@ def lib():
         L.emu_field_op.argtypes = [i32, i32, vp, vp, vp]
         L.emu_field_op_dev.argtypes = [i32, i32, vp, vp, vp]
         L.emu_dev_field_info.argtypes = [i32, vp, vp]
+        L.emu_ec_op.argtypes = [i32, i32, vp, vp, vp, sz]
         L.emu_msm_host.argtypes = [i32, i32, i32, vp, vp, vp, sz, i32, i32]
         L.emu_msm_table.argtypes = [i32, i32, i32, vp, vp, vp, sz, sz, i32, i32, i32]
         L.emu_sum_reduce.argtypes = [i32, i32, vp, vp, sz, i32]
@@ -155,6 +156,20 @@ def field_op_dev(curve, op, a, b=None):
     out = np.zeros(64, dtype=np.uint32)
     nl = lib().emu_field_op_dev(CURVE_ID[curve], op, _p(a), _p(b), _p(out))
     return out[:nl]
+
+
+def ec_op(curve, op, a, b, rec_words):
+    """Group-law probe (msm_bodies.h ec_probe): a, b are (n, rec_words) uint32 raw device records XYZZ<FD>.
+    Returns (n, rec_words + 1) uint32: the result record and its flag word; None for an op the curve does not have."""
+    a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1, rec_words)
+    b = np.ascontiguousarray(b, dtype=np.uint32).reshape(-1, rec_words)
+    assert a.shape == b.shape
+    out = np.zeros((a.shape[0], rec_words + 1), dtype=np.uint32)
+    rw = lib().emu_ec_op(CURVE_ID[curve], op, _p(a), _p(b), _p(out), a.shape[0])
+    if rw < 0:
+        return None
+    assert rw == rec_words, (rw, rec_words)
+    return out
 
 
 def sum_reduce(curve, points, out_kind=0, K=0):

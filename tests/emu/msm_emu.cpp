@@ -218,6 +218,9 @@ struct EmuOps {
   void (*fop)(int op, const void* a, const void* b, void* r);
   int (*fop_dev)(int op, const void* a, const void* b, void* r);
   int (*dev_info)(int* lb, int* nl);
+  // group-law probe (msm_bodies.h ec_probe) over n raw XYZZ<FD> records; returns the 32-bit words of a record, -1 for an op
+  // this curve does not have; out = n x (record, flag word)
+  int (*ec_op)(int op, const void* a, const void* b, void* out, size_t n);
   int (*sum_reduce)(int out_kind, void* r, const void* points, size_t n, int K);
   void (*batch_affine)(int src_kind, void* dst, const void* src, size_t n, int K);
   // ticket order: submit A, then two complete MSMs B and C while A is outstanding, then finish A; r3 = 3 affine results;
@@ -337,6 +340,18 @@ struct EmuCurve {
     }
     return 0;
   }
+  static int ec_op(int op, const void* a, const void* b, void* out, size_t n) {
+    if (!ec_probe_has<FD>(op) || op >= EC_PROBE_QUAD) return -1;   // the four-lane forms are a GPU launch shape
+    constexpr size_t RW = sizeof(XYZZ<FD>) / 4;
+    for (size_t j = 0; j < n; j++) {
+      XYZZ<FD> r;
+      const uint32_t inf = ec_probe<FD>(op, ((const XYZZ<FD>*)a)[j], ((const XYZZ<FD>*)b)[j], r);
+      uint32_t* o = (uint32_t*)out + j * (RW + 1);
+      memcpy(o, &r, sizeof(r));
+      o[RW] = inf;
+    }
+    return (int)RW;
+  }
   static int sum_reduce(int out_kind, void* r, const void* points, size_t n, int K) {
     EmuBackend bk;
     MsmEngine<C, EmuBackend> eng(bk);
@@ -400,10 +415,10 @@ struct EmuCurve {
     // twisted Edwards: no Jacobian / projective batch conversion and no KZG quotient, as the engine refuses them (is_weierstrass);
     // the dispatcher answers -1 for an absent operation
     if constexpr (IsEdwards<F>::value) {
-      static const EmuOps o = {msm, msm_host, msm_table, gen, fop, fop_dev, dev_info, sum_reduce, nullptr, msm_slots, nullptr};
+      static const EmuOps o = {msm, msm_host, msm_table, gen, fop, fop_dev, dev_info, ec_op, sum_reduce, nullptr, msm_slots, nullptr};
       return &o;
     } else {
-      static const EmuOps o = {msm, msm_host, msm_table, gen, fop, fop_dev, dev_info, sum_reduce, batch_affine, msm_slots, fr_quotient};
+      static const EmuOps o = {msm, msm_host, msm_table, gen, fop, fop_dev, dev_info, ec_op, sum_reduce, batch_affine, msm_slots, fr_quotient};
       return &o;
     }
   }
@@ -490,6 +505,10 @@ int emu_field_op(int curve, int op, const void* a, const void* b, void* r) {
 int emu_field_op_dev(int curve, int op, const void* a, const void* b, void* r) {
   const EmuOps* o = ops_of(curve);
   return o ? o->fop_dev(op, a, b, r) : 0;
+}
+int emu_ec_op(int curve, int op, const void* a, const void* b, void* out, size_t n) {
+  const EmuOps* o = ops_of(curve);
+  return o ? o->ec_op(op, a, b, out, n) : -1;
 }
 int emu_sum_reduce(int curve, int out_kind, void* r, const void* points, size_t n, int K) {
   const EmuOps* o = ops_of(curve);

@@ -546,3 +546,77 @@ def test_three_banderwagon_tickets_in_flight(dev, torch_cuda):
         assert _prj(cb.finish(t[0], coord="prj")) == expect[0]
     finally:
         cb.close()
+
+
+# ----------------------------------------------------------------------------------------------
+# the forms the defaults never take (tests/test_gpu_parity.py has the short Weierstrass curves)
+# ----------------------------------------------------------------------------------------------
+MERGE_OPTION_DEFAULTS = {"c": 0, "K": 0, "merge_chain": 0, "merge_queue_quad": 0, "merge_lmax": 0}
+
+
+def test_forced_merge_forms(dev, torch_cuda):
+    """Both forms of the head merge by option -- merge_chain 1 (queue) / 2 (tree) x merge_queue_quad 0 / 2 (one lane per chain) x
+    merge_lmax 0 (= 8), 1, 2, 64 -- under the automatic plan, a plan with few buckets and few entries per lane (chains of hundreds of
+    heads) and c = 16; uniform scalars, all equal, a quarter equal, all points equal, all points and scalars equal.  In the four-lane
+    kernels lane 0 of a quad runs the unified law alone for this curve; the one-lane queue kernel and k_merge_long run nowhere else."""
+    n, seed = 60000, 2300
+    d_pts = _synth(dev, torch_cuda, seed, n)
+    logs = _logs(seed, n)
+    d_one = d_pts[:1].repeat(n, 1).contiguous()
+    sc = _rand_scalars(2301, n)
+    sc_eq = np.tile(sc[:1], (n, 1))
+    sc_q = sc.copy()
+    sc_q[::4] = sc[1]
+    inputs = [("uniform", sc, d_pts, _by_logs(sc, logs)), ("all scalars equal", sc_eq, d_pts, _by_logs(sc_eq, logs)),
+              ("a quarter equal", sc_q, d_pts, _by_logs(sc_q, logs)),
+              ("all points equal", sc, d_one, bw.mul(sum(_ints(sc)) * logs[0] % bw.R, bw.G)),
+              ("all points and scalars equal", sc_eq, d_one, bw.mul(_ints(sc[:1])[0] * n * logs[0] % bw.R, bw.G))]
+    try:
+        for label, s, dp, expect in inputs:
+            ds = _to_dev(torch_cuda, s)
+            for k, v in MERGE_OPTION_DEFAULTS.items():
+                dev.set_option(k, v)
+            default = bytes(dev.msm("banderwagon", ds, dp, n, coord="aff"))
+            assert bw.aff_from(default) == expect, (label, dev.last_plan())
+            for c, K in ((0, 0), (6, 4), (16, 0)):
+                dev.set_option("c", c)
+                dev.set_option("K", K)
+                for mc in (1, 2):
+                    for mq in (0, 2):
+                        for ml in (0, 1, 2, 64):
+                            dev.set_option("merge_chain", mc)
+                            dev.set_option("merge_queue_quad", mq)
+                            dev.set_option("merge_lmax", ml)
+                            got = bytes(dev.msm("banderwagon", ds, dp, n, coord="aff"))
+                            assert bw.aff_from(got) == expect and got == default, (label, c, K, mc, mq, ml, dev.last_plan())
+    finally:
+        for k, v in MERGE_OPTION_DEFAULTS.items():
+            dev.set_option(k, v)
+
+
+@pytest.mark.parametrize("quad", ["0", "2000000000"])
+def test_reduction_all_wide_or_all_narrow(quad, torch_cuda):
+    """Contexts created under $CTT_HIP_MSM_QUAD = 0 (every reduction pass through k_pyr) and above any pass (every pass through
+    k_pyr_quad, where lane 0 of a quad adds alone for this curve): 2^16 pairs, uniform inputs and all points equal."""
+    from constantine_amd import DeviceMsm
+    n, seed = 1 << 16, 2400
+    old = os.environ.get("CTT_HIP_MSM_QUAD")
+    os.environ["CTT_HIP_MSM_QUAD"] = quad
+    try:
+        eng = DeviceMsm(0)
+    finally:
+        if old is None:
+            os.environ.pop("CTT_HIP_MSM_QUAD", None)
+        else:
+            os.environ["CTT_HIP_MSM_QUAD"] = old
+    try:
+        d_pts = _synth(eng, torch_cuda, seed, n)
+        logs = _logs(seed, n)
+        sc = _rand_scalars(2401, n)
+        ds = _to_dev(torch_cuda, sc)
+        for label, dp, expect in (("uniform", d_pts, _by_logs(sc, logs)),
+                                  ("all points equal", d_pts[:1].repeat(n, 1).contiguous(), bw.mul(sum(_ints(sc)) * logs[0] % bw.R, bw.G))):
+            for _ in range(2):
+                assert bw.aff_from(bytes(eng.msm("banderwagon", ds, dp, n, coord="aff"))) == expect, (label, quad, eng.last_plan())
+    finally:
+        eng.close()

@@ -1132,3 +1132,141 @@ def test_concurrent_callers_are_serialised():
         t.join()
     for k, job in enumerate(jobs):
         assert results[k] == job[4], job[0]
+
+
+# ----------------------------------------------------------------------------------------------
+# the forms the defaults never take: every merge form by option, all-wide / all-narrow reductions, the optional stream placements
+# ----------------------------------------------------------------------------------------------
+MERGE_SWEEP = [(mc, mq, ml) for mc in (1, 2) for mq in (0, 2) for ml in (0, 1, 2, 64)]   # merge_chain, merge_queue_quad, merge_lmax
+MERGE_OPTION_DEFAULTS = {"c": 0, "K": 0, "merge_chain": 0, "merge_queue_quad": 0, "merge_lmax": 0}
+
+
+def _adversarial_inputs(name, n, seed):
+    """(label, scalars, points): uniform; all scalars equal; a quarter equal; all points equal; all points and all scalars equal"""
+    curve = po.CURVES[name]
+    pts = cref.gen_points(name, seed, n)
+    sc = cref.synth_scalars(seed + 1, n, curve.scalar_bits)
+    sc_eq = np.tile(sc[:1], (n, 1))
+    sc_q = sc.copy()
+    sc_q[::4] = sc[1]
+    pts_eq = np.tile(pts[:1], (n, 1))
+    return [("uniform", sc, pts), ("all scalars equal", sc_eq, pts), ("a quarter equal", sc_q, pts), ("all points equal", sc, pts_eq),
+            ("all points and scalars equal", sc_eq, pts_eq)]
+
+
+@pytest.mark.parametrize("name", ["bls12_381_g1", "bn254_snarks_g1", "pallas", "bls12_381_g2", "bn254_snarks_g2"])
+def test_forced_merge_forms(name, dev, torch_cuda):
+    """The head merge has two forms and the plan picks one (plan_merge_lmax): the queue form (k_merge_tail_queue, then k_merge_queue_quad
+    with four lanes per chain or k_merge_queue with one, then k_merge_long for the chains beyond merge_lmax) and the tree
+    (k_merge_tail, k_merge_step[_quad], k_merge_finish).  By default the G2 curves never take the queue form, the one-lane queue kernel
+    runs nowhere and the G1 curves take the tree only where the plan happens to.  Here every form is forced -- merge_chain 1 (queue) /
+    2 (tree) x merge_queue_quad 0 / 2 (one lane) x merge_lmax 0 (= 8), 1, 2, 64 -- under the automatic plan, under a plan with few
+    buckets and few entries per lane (chains of hundreds of heads) and under c = 16, on uniform inputs and on the inputs whose additions
+    are P + P or whose chains are as long as they get.  Every result byte-equal to the oracle's and to the default options' result."""
+    torch = torch_cuda
+    n = 60000 if name in G1S else 5000
+    try:
+        for label, sc, pts in _adversarial_inputs(name, n, 2300):
+            expect = bytes(cref.msm(name, sc, pts, nthreads=NT)[0])
+            ds, dp = _to_dev(torch, sc), _to_dev(torch, pts)
+            for k, v in MERGE_OPTION_DEFAULTS.items():
+                dev.set_option(k, v)
+            default = bytes(dev.msm(name, ds, dp, n, coord="aff"))
+            assert default == expect, (label, dev.last_plan())
+            for c, K in ((0, 0), (6, 4), (16, 0)):
+                dev.set_option("c", c)
+                dev.set_option("K", K)
+                for mc, mq, ml in MERGE_SWEEP:
+                    dev.set_option("merge_chain", mc)
+                    dev.set_option("merge_queue_quad", mq)
+                    dev.set_option("merge_lmax", ml)
+                    got = bytes(dev.msm(name, ds, dp, n, coord="aff"))
+                    assert got == expect and got == default, (label, c, K, mc, mq, ml, dev.last_plan())
+    finally:
+        for k, v in MERGE_OPTION_DEFAULTS.items():
+            dev.set_option(k, v)
+
+
+def _context_under(var, value):
+    """a fresh context created while the environment variable has this value (read once, when the context is created)"""
+    from constantine_amd import DeviceMsm
+    old = os.environ.get(var)
+    os.environ[var] = value
+    try:
+        return DeviceMsm(0)
+    finally:
+        if old is None:
+            os.environ.pop(var, None)
+        else:
+            os.environ[var] = old
+
+
+@pytest.mark.parametrize("quad", ["0", "2000000000"])
+@pytest.mark.parametrize("name", ["bn254_snarks_g1", "bls12_381_g2"])
+def test_reduction_all_wide_or_all_narrow(name, quad, torch_cuda):
+    """The bucket reduction hands a pass to k_pyr (one lane per addition) or to k_pyr_quad (four) by its number of additions against
+    $CTT_HIP_MSM_QUAD, 49152 by default -- the only split any other test runs.  Contexts created under 0 (every pass through k_pyr) and
+    under a value above any pass (every pass through k_pyr_quad), 2^16 pairs, uniform inputs and all points equal."""
+    torch = torch_cuda
+    curve = po.CURVES[name]
+    n = 1 << 16
+    eng = _context_under("CTT_HIP_MSM_QUAD", quad)
+    try:
+        pts = cref.gen_points(name, 2400, n)
+        sc = cref.synth_scalars(2401, n, curve.scalar_bits)
+        for label, p in (("uniform", pts), ("all points equal", np.tile(pts[:1], (n, 1)))):
+            expect = bytes(cref.msm(name, sc, p, nthreads=NT)[0])
+            ds, dp = _to_dev(torch, sc), _to_dev(torch, p)
+            for _ in range(2):
+                assert bytes(eng.msm(name, ds, dp, n, coord="aff")) == expect, (label, quad, eng.last_plan())
+    finally:
+        eng.close()
+
+
+STREAM_PLACEMENTS = [{"early_tail": 0}, {"early_tail": 2}, {"front_side": 1}, {"front_side": 2}, {"pyr0_tail": 1},
+                     {"early_tail": 2, "front_side": 1}]
+STREAM_OPTION_DEFAULTS = {"early_tail": 1, "front_side": 0, "pyr0_tail": 0}   # msm_pipeline.h MsmOptions
+
+
+@pytest.mark.parametrize("name", ["bls12_381_g1", "bn254_snarks_g1"])
+def test_pipelined_stream_placements(name, dev, torch_cuda):
+    """Where the stages of a pipelined MSM run is a set of options nothing else sets: early_tail (merge and every reduction pass on
+    the tail stream: 0 never, 2 whenever pipelining), front_side (conversion and sort on the front stream: 1 whenever pipelining, 2
+    never), pyr0_tail (the first reduction pass on the tail stream).  Three tickets in flight -- 3000, 70000 and 2^18 + 5 pairs --
+    finished out of order, under each setting; the same over a window table of cached bases for early_tail; then a blocking call
+    with the options back at their defaults."""
+    from constantine_amd import CachedBases
+    torch = torch_cuda
+    curve = po.CURVES[name]
+    sizes = (3000, 70000, (1 << 18) + 5)
+    nmax = max(sizes)
+    pts = cref.gen_points(name, 2500, nmax)
+    scs = [cref.synth_scalars(2501 + i, m, curve.scalar_bits) for i, m in enumerate(sizes)]
+    expect = [bytes(cref.msm(name, s, pts[:m], nthreads=NT)[0]) for s, m in zip(scs, sizes)]
+    dp = _to_dev(torch, pts)
+    dss = [_to_dev(torch, s) for s in scs]
+
+    def set_all(opts):
+        for k, v in STREAM_OPTION_DEFAULTS.items():
+            dev.set_option(k, opts.get(k, v))
+    try:
+        for opts in STREAM_PLACEMENTS:
+            set_all(opts)
+            for order in ((2, 0, 1), (0, 1, 2), (1, 2, 0)):
+                t = [dev.submit(name, dss[i], dp, sizes[i]) for i in range(3)]
+                for i in order:
+                    assert bytes(dev.finish(t[i], coord="aff")) == expect[i], (opts, order, i)
+        bases = CachedBases(name, dp, ctx=dev.ctx, on_device=True, table=True)
+        try:
+            for opts in ({"early_tail": 0}, {"early_tail": 2}):
+                set_all(opts)
+                for order in ((2, 0, 1), (1, 0, 2)):
+                    t = [bases.submit(dss[i], sizes[i]) for i in range(3)]
+                    for i in order:
+                        assert bytes(bases.finish(t[i], coord="aff")) == expect[i], ("table", opts, order, i)
+        finally:
+            bases.close()
+    finally:
+        set_all({})
+    for i in (1, 0, 2):
+        assert bytes(dev.msm(name, dss[i], dp, sizes[i], coord="aff")) == expect[i], i
