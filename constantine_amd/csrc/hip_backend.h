@@ -461,20 +461,19 @@ __global__ void k_field_op_dev(int op, const F* a, const F* b, FD* r, uint32_t n
   if constexpr (FD::UNSAT) r[j] = dev_field_probe<FD>(op, FD::from_sat(a[j]), FD::from_sat(b[j]));
 }
 
-// field-op probe for the GPU unit tests: op 0 mul, 1 sqr, 2 add, 3 sub, 4 neg
+// field-op probe for the GPU unit tests (msm_bodies.h field_probe): op 0 mul, 1 sqr, 2 add, 3 sub, 4 neg, 5 inv, 6 inv_fermat
 template <class F>
 __global__ void k_field_op(int op, const F* a, const F* b, F* r, uint32_t n) {
   uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
-  F x = a[j], y = b[j], o;
-  switch (op) {
-    case 0: o = F::mul(x, y); break;
-    case 1: o = F::sqr(x); break;
-    case 2: o = F::add(x, y); break;
-    case 3: o = F::sub(x, y); break;
-    default: o = F::neg(x); break;
-  }
-  r[j] = o;
+  r[j] = field_probe<F>(op, a[j], b[j]);
+}
+// the same over the curve's scalar field, one lane per element: 0 .. 6 as above, 7 from_mont, 8 to_mont
+template <class Fr>
+__global__ void k_fr_op(int op, const Fr* a, const Fr* b, Fr* r, uint32_t n) {
+  uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  r[j] = field_probe<Fr>(op, a[j], b[j]);
 }
 
 // probe of the group law (msm_bodies.h ec_probe): raw XYZZ<FD> records in; out, per result record, the record and one flag word
@@ -1006,7 +1005,18 @@ struct CurveImpl {
     HIP_CHECK(hipStreamSynchronize(bk->stream));
   }
   static bool probe_has(int op) { return ec_probe_has<FD>(op); }
+  // (the caller, ctt_hip_field_op, has refused every op outside the tables)
   static void field_op(HipBackend* bk, int op, const void* d_a, const void* d_b, void* d_r, uint32_t n) {
+    if (op >= FIELD_PROBE_FR) {  // the scalar field
+      using Fr = typename C::Fr;
+      if (n == 0) return;
+      hipLaunchKernelGGL(k_fr_op<Fr>, dim3((n + 255) / 256), dim3(256), 0, bk->stream, op - FIELD_PROBE_FR, (const Fr*)d_a,
+                         (const Fr*)d_b, (Fr*)d_r, n);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipStreamSynchronize(bk->stream));
+      return;
+    }
+    if (op >= FIELD_PROBE_F) op -= FIELD_PROBE_F;   // the coordinate field under its every-curve numbers: the kernel of ops 0 .. 6
     if (op >= 32) {  // group-law probe over raw XYZZ<FD> records (the caller has checked ec_probe_has)
       const int eop = op - 32;
       using Rec = XYZZ<FD>;

@@ -934,6 +934,37 @@ CTT_HD void fr_quotient_out_body(const FrQuotientArgs<Fr>& a, uint32_t i) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Probes of the reference-representation fields for the unit tests (GPU: k_field_op / k_fr_op, CPU: tests/emu); the caller has
+// checked the op (field_probe_has):
+//   0 mul   1 sqr   2 add   3 sub   4 neg   5 inv (modinv.h)   6 inv_fermat (Fp2: inv again)
+//   7 from_mont   8 to_mont                                      (prime fields only: the scalar-field probe)
+// ---------------------------------------------------------------------------------------------
+static constexpr int FIELD_PROBE_END = 7;   // coordinate field: 0 .. 6
+static constexpr int FR_PROBE_END = 9;      // scalar field: 0 .. 8
+// numbers of ctt_hip_field_op: FIELD_PROBE_F + k the coordinate field of every curve (the short Weierstrass curves have it as k,
+// too), FIELD_PROBE_FR + k the scalar field.  (32 .. 51 is the group law, ec_probe below.)
+static constexpr int FIELD_PROBE_F = 64, FIELD_PROBE_FR = 80;
+CTT_HD bool field_probe_has(int op, int end) { return op >= 0 && op < end; }
+template <class F>
+CTT_HD F field_probe(int op, const F& x, const F& y) {
+  switch (op) {
+    case 0: return F::mul(x, y);
+    case 1: return F::sqr(x);
+    case 2: return F::add(x, y);
+    case 3: return F::sub(x, y);
+    case 4: return F::neg(x);
+    case 5: return F::inv(x);
+    case 6:
+      if constexpr (IsFp2<F>::value) return F::inv(x); else return F::inv_fermat(x);
+  }
+  if constexpr (!IsFp2<F>::value) {
+    if (op == 7) return F::from_mont(x);
+    if (op == 8) return F::to_mont(x);
+  }
+  return F::zero();   // (not reached: field_probe_has)
+}
+
+// ---------------------------------------------------------------------------------------------
 // Probe of the device field FD for the unit tests (GPU: k_field_op_dev, CPU: tests/emu), operands x, y < 2p:
 //   0 mul   1 sqr   2 add   3 sub<2>   4 conversion only
 //   5, 6, 7  products with operands at the largest bounds -- and in the lazy forms -- that xyzz_madd feeds them

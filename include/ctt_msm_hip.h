@@ -260,9 +260,14 @@ int ctt_hip_msm_last_timings(ctt_hip_msm_ctx* ctx, float* ms, int cap);
 int ctt_hip_msm_last_plan(ctt_hip_msm_ctx* ctx, int* out, int cap);
 /* d_out[i] = [s_i]G, deterministic synthetic subgroup points (bench / test inputs) */
 int ctt_hip_gen_points(ctt_hip_msm_ctx* ctx, int curve, uint64_t seed, uint64_t first, uint32_t n, void* d_out);
-/* kernel unit tests on device arrays.  op 0 .. 4: element-wise coordinate-field op (0 mul, 1 sqr, 2 add, 3 sub, 4 neg), operands
- * and result in the C-API representation; 16 .. 23: the same operands through the device field, raw device limbs out (curves that
- * compute in the carry-free field).  Both refused (-1) for Banderwagon.
+/* kernel unit tests on device arrays.  op 0 .. 6: element-wise coordinate-field op (0 mul, 1 sqr, 2 add, 3 sub, 4 neg, 5 inverse by
+ * division steps, 6 inverse by Fermat's exponent -- over Fp2 the same as 5; the inverse of 0 is 0), operands and result in the C-API
+ * representation; 16 .. 23: the same operands through the device field, raw device limbs out (curves that compute in the carry-free
+ * field).  Both refused (-1) for Banderwagon.
+ * op 64 + k, k = 0 .. 6: the coordinate-field ops again, every curve (Banderwagon's field is reached here).
+ * op 80 + k, k = 0 .. 8: the same table over the curve's scalar field, every curve: rows of 32 bytes, Montgomery residues; 7 from_mont
+ * (residue -> canonical words), 8 to_mont (the reverse).
+ * Every op outside these tables and the group law's below is refused (-1) and nothing is launched.
  * op 32 + k: the group law, every curve.  d_a, d_b: n raw device records (X, Y, ZZ, ZZZ; for Banderwagon X, Y, Z, T), 32-bit words in
  * the device representation of the coordinate field -- the caller chooses the representative of every coordinate.  d_r: per result
  * record, the record followed by one flag word (1 = the code takes it for the neutral element).  k = 0 .. 3 the mixed addition of the

@@ -35,6 +35,8 @@ def lib():
         L.emu_msm.argtypes = [i32, i32, i32, vp, vp, vp, sz, i32, i32, i32, vp]
         L.emu_gen_points.argtypes = [i32, u64, u64, u32, vp]
         L.emu_field_op.argtypes = [i32, i32, vp, vp, vp]
+        L.emu_field_op_n.argtypes = [i32, i32, vp, vp, vp, sz]
+        L.emu_fr_op.argtypes = [i32, i32, vp, vp, vp, sz]
         L.emu_field_op_dev.argtypes = [i32, i32, vp, vp, vp]
         L.emu_dev_field_info.argtypes = [i32, vp, vp]
         L.emu_ec_op.argtypes = [i32, i32, vp, vp, vp, sz]
@@ -139,6 +141,27 @@ def field_op(curve, op, a, b=None):
     b = a if b is None else np.ascontiguousarray(b, dtype=np.uint8)
     out = np.zeros_like(a)
     lib().emu_field_op(CURVE_ID[curve], op, _p(a), _p(b), _p(out))
+    return out
+
+
+def field_op_n(curve, op, a, b=None):
+    """Coordinate-field probe over the rows of a (and b): ops 0 .. 6 (msm_bodies.h field_probe); None for an op outside the table."""
+    return _rows_op(lib().emu_field_op_n, curve, op, a, b)
+
+
+def fr_op(curve, op, a, b=None):
+    """Scalar-field probe over rows of 32 bytes: ops 0 .. 8 (7 from_mont, 8 to_mont); None for an op outside the table."""
+    return _rows_op(lib().emu_fr_op, curve, op, a, b)
+
+
+def _rows_op(fn, curve, op, a, b):
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    b = a if b is None else np.ascontiguousarray(b, dtype=np.uint8)
+    assert a.ndim == 2 and a.shape == b.shape
+    out = np.full_like(a, 0xA5)
+    if fn(CURVE_ID[curve], op, _p(a), _p(b), _p(out), a.shape[0]) != 0:
+        assert (out == 0xA5).all()   # a refused op writes nothing
+        return None
     return out
 
 

@@ -215,7 +215,8 @@ struct EmuOps {
   int (*msm_table)(int coef_is_fr, int out_kind, void* r, const void* coefs, const void* points, size_t ntab, size_t n, int c,
                    int K, int chunks);
   void (*gen)(uint64_t seed, uint64_t first, uint32_t n, void* out);
-  void (*fop)(int op, const void* a, const void* b, void* r);
+  int (*fop)(int op, const void* a, const void* b, void* r, size_t n);
+  int (*fr_op)(int op, const void* a, const void* b, void* r, size_t n);
   int (*fop_dev)(int op, const void* a, const void* b, void* r);
   int (*dev_info)(int* lb, int* nl);
   // group-law probe (msm_bodies.h ec_probe) over n raw XYZZ<FD> records; returns the 32-bit words of a record, -1 for an op
@@ -308,20 +309,18 @@ struct EmuCurve {
     Affine<F> G = generator<C>();
     for (uint32_t j = 0; j < n; j++) gen_point_body<F>(G, seed, first, n, (Affine<F>*)out, j);
   }
-  // field-level probes: op 0 mul, 1 sqr, 2 add, 3 sub, 4 neg, 5 inv  (coordinate field, reference representation)
-  static void fop(int op, const void* a, const void* b, void* r) {
-    const F& x = *(const F*)a;
-    const F& y = *(const F*)b;
-    F& o = *(F*)r;
-    switch (op) {
-      case 0: o = F::mul(x, y); break;
-      case 1: o = F::sqr(x); break;
-      case 2: o = F::add(x, y); break;
-      case 3: o = F::sub(x, y); break;
-      case 4: o = F::neg(x); break;
-      case 5: o = F::inv(x); break;
-      case 6: if constexpr (!IsFp2<F>::value) o = F::inv_fermat(x); else o = F::inv(x); break;
-    }
+  // field-level probes (msm_bodies.h field_probe) over n elements: the coordinate field in the reference representation, ops 0 .. 6,
+  // and the scalar field, ops 0 .. 8; -1 for an op outside the table, nothing written
+  static int fop(int op, const void* a, const void* b, void* r, size_t n) {
+    if (!field_probe_has(op, FIELD_PROBE_END)) return -1;
+    for (size_t j = 0; j < n; j++) ((F*)r)[j] = field_probe<F>(op, ((const F*)a)[j], ((const F*)b)[j]);
+    return 0;
+  }
+  static int fr_op(int op, const void* a, const void* b, void* r, size_t n) {
+    using Fr = typename C::Fr;
+    if (!field_probe_has(op, FR_PROBE_END)) return -1;
+    for (size_t j = 0; j < n; j++) ((Fr*)r)[j] = field_probe<Fr>(op, ((const Fr*)a)[j], ((const Fr*)b)[j]);
+    return 0;
   }
   // device-field probe: inputs in the reference representation, output raw FD limbs (uint32[NL]); returns NL
   static int fop_dev(int op, const void* a, const void* b, void* r) {
@@ -415,10 +414,10 @@ struct EmuCurve {
     // twisted Edwards: no Jacobian / projective batch conversion and no KZG quotient, as the engine refuses them (is_weierstrass);
     // the dispatcher answers -1 for an absent operation
     if constexpr (IsEdwards<F>::value) {
-      static const EmuOps o = {msm, msm_host, msm_table, gen, fop, fop_dev, dev_info, ec_op, sum_reduce, nullptr, msm_slots, nullptr};
+      static const EmuOps o = {msm, msm_host, msm_table, gen, fop, fr_op, fop_dev, dev_info, ec_op, sum_reduce, nullptr, msm_slots, nullptr};
       return &o;
     } else {
-      static const EmuOps o = {msm, msm_host, msm_table, gen, fop, fop_dev, dev_info, ec_op, sum_reduce, batch_affine, msm_slots, fr_quotient};
+      static const EmuOps o = {msm, msm_host, msm_table, gen, fop, fr_op, fop_dev, dev_info, ec_op, sum_reduce, batch_affine, msm_slots, fr_quotient};
       return &o;
     }
   }
@@ -498,9 +497,16 @@ int emu_gen_points(int curve, uint64_t seed, uint64_t first, uint32_t n, void* o
 }
 int emu_field_op(int curve, int op, const void* a, const void* b, void* r) {
   const EmuOps* o = ops_of(curve);
-  if (!o) return -1;
-  o->fop(op, a, b, r);
-  return 0;
+  return o ? o->fop(op, a, b, r, 1) : -1;
+}
+// n elements at once; the scalar field C::Fr (rows of 32 bytes) with the same table and 7 from_mont, 8 to_mont
+int emu_field_op_n(int curve, int op, const void* a, const void* b, void* r, size_t n) {
+  const EmuOps* o = ops_of(curve);
+  return o ? o->fop(op, a, b, r, n) : -1;
+}
+int emu_fr_op(int curve, int op, const void* a, const void* b, void* r, size_t n) {
+  const EmuOps* o = ops_of(curve);
+  return o ? o->fr_op(op, a, b, r, n) : -1;
 }
 int emu_field_op_dev(int curve, int op, const void* a, const void* b, void* r) {
   const EmuOps* o = ops_of(curve);

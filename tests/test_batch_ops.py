@@ -72,6 +72,73 @@ def test_emu_batch_affine(name, kind):
     assert bytes(emu.batch_affine(name, src1, 1 if kind == "jac" else 2, K=8)) == bytes(exp1)
 
 
+# ---- edge rows: the Z values and neutral patterns at which one inversion per lane can go wrong ---------------------------------
+EDGE_CURVES = ["bls12_381_g1", "bn254_snarks_g1", "pallas", "bls12_381_g2"]
+EDGE_K = (1, 2, 3, 8, 64)
+_EDGE_AFF = {}
+
+
+def edge_sizes(K):
+    return [max(1, n) for n in (1, K - 1, K, K + 1, 2 * K + 1, 37 * K - 1)]
+
+
+def edge_rows(name, kind, K, n, off):
+    """n rows in lanes of K consecutive rows; the lane's number + off picks its pattern:
+    0 every Z = 1;  1 every Z = p - 1;  2 Z, 1/Z, Z', 1/Z', ... (the lane's running product comes back to one at every other row);
+    3 every row neutral (between the ordinary lanes 2 and 4);  4 random Z with neutrals at the lane's first and last row.
+    Returns (rows, the affine rows they were made from -- zeros for a neutral)."""
+    curve = po.CURVES[name]
+    F = curve.F
+    if name not in _EDGE_AFF:
+        _EDGE_AFF[name] = cref.gen_points(name, 23, 37 * max(EDGE_K) - 1)
+    aff = _EDGE_AFF[name][:n]
+    rng = random.Random("batch-affine-edge-%s-%s-%d-%d" % (name, kind, K, n))
+    one, zero = F.from_int(1), F.from_int(0)
+    rows, expect = [], np.array(aff, copy=True)
+    prev = None
+    for i in range(n):
+        lane, j = divmod(i, K)
+        pat = (lane + off) % 5
+        last = j == K - 1 or i == n - 1
+        if pat == 0:
+            z = one
+        elif pat == 1:
+            z = F.neg(one)
+        elif pat == 2:
+            z = F.inv(prev) if j % 2 else _rand_fe(F, rng)
+            prev = z
+        elif pat == 3 or j == 0 or last:
+            z = zero
+        else:
+            z = _rand_fe(F, rng)
+        P = curve.aff_from_bytes(bytes(aff[i]))
+        assert P is not None
+        if F.is_zero(z):
+            x, y = _rand_fe(F, rng), _rand_fe(F, rng)
+            expect[i] = 0
+        elif kind == "jac":
+            z2 = F.sqr(z)
+            x, y = F.mul(P[0], z2), F.mul(P[1], F.mul(z2, z))
+        else:
+            x, y = F.mul(P[0], z), F.mul(P[1], z)
+        rows.append(F.to_mont_bytes(x) + F.to_mont_bytes(y) + F.to_mont_bytes(z))
+    return np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(n, -1).copy(), expect
+
+
+def edge_cases(name, kind):
+    for K in EDGE_K:
+        for off, n in enumerate(edge_sizes(K)):
+            yield (K, n) + edge_rows(name, kind, K, n, off)
+
+
+@pytest.mark.parametrize("name", EDGE_CURVES)
+@pytest.mark.parametrize("kind", ["jac", "prj"])
+def test_emu_batch_affine_edge_rows(name, kind):
+    for K, n, src, expect in edge_cases(name, kind):
+        got = emu.batch_affine(name, src, 1 if kind == "jac" else 2, K=K)
+        assert bytes(got) == bytes(expect), (name, kind, K, n, np.nonzero((got != expect).any(axis=1))[0][:4])
+
+
 @pytest.mark.parametrize("name", ALL)
 def test_emu_sum_reduce(name):
     curve = po.CURVES[name]
@@ -100,6 +167,28 @@ def test_gpu_batch_affine_constantine_symbol(name, kind):
     src, expect = make_nonaffine(name, aff, kind, rng, neutral_at={0, 7, 8, 9, 150, n - 1})
     assert bytes(batchAffine_vartime(name, src, coord=kind)) == bytes(expect)
     assert batchAffine_vartime(name, src[:0], coord=kind).shape[0] == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", EDGE_CURVES)
+@pytest.mark.parametrize("kind", ["jac", "prj"])
+def test_gpu_batch_affine_edge_rows(name, kind):
+    """the same rows through ctt_hip_batch_affine on device arrays, the lane span forced through the option K"""
+    import torch
+    from constantine_amd import DeviceMsm, CURVES
+    eng = DeviceMsm(0)
+    try:
+        for K, n, src, expect in edge_cases(name, kind):
+            eng.set_option("K", K)
+            d_src = torch.from_numpy(src).cuda()
+            d_out = torch.full((n, CURVES[name].aff_bytes), 0xA5, dtype=torch.uint8, device="cuda")
+            eng.batch_affine(name, d_out, d_src, n, src_coord=kind)
+            torch.cuda.synchronize()
+            got = d_out.cpu().numpy()
+            assert bytes(got) == bytes(expect), (name, kind, K, n, np.nonzero((got != expect).any(axis=1))[0][:4])
+    finally:
+        eng.set_option("K", 0)
+        eng.close()
 
 
 @pytest.mark.gpu

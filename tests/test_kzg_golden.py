@@ -359,3 +359,71 @@ def test_quotient_polynomial_on_device_matches_the_host_formula():
         assert rc == 0 and y == want_y
         assert [int.from_bytes(bytes(row), "little") for row in d_q.cpu().numpy()] == want_q
     assert device_quotient(poly_le, dom[5])[0] == -2
+
+
+def _degenerate_quotient_cases():
+    """(label, poly, z, expected q, expected y): the zero and a constant polynomial, z in {0, 2, r - 2}, alternating 0 and r - 1;
+    expected values from the spec formula (for the first two also stated outright)"""
+    import random
+
+    from oracle import kzg_spec as ks
+    r = ks.R
+    n = ks.FIELD_ELEMENTS_PER_BLOB
+    rng = random.Random(46)
+    c = rng.randrange(1, r)
+    rand = [rng.randrange(r) for _ in range(n)]
+    alt = [0 if i % 2 == 0 else r - 1 for i in range(n)]
+    cases = [("zero polynomial", [0] * n, rng.randrange(r)), ("constant polynomial", [c] * n, rng.randrange(r)),
+             ("constant r - 1", [r - 1] * n, 2)]
+    for z in (0, 2, r - 2):
+        cases += [("random polynomial, z = %d" % (z if z < 3 else z - r), rand, z), ("alternating 0 and r - 1", alt, z)]
+    cases.append(("alternating 0 and r - 1, random z", alt, rng.randrange(r)))
+    out = []
+    for label, poly, z in cases:
+        assert pow(z, n, r) != 1, label
+        want_q, want_y = ks.quotient_polynomial(poly, z)
+        if label.startswith(("zero", "constant")):
+            assert want_y == poly[0] and not any(want_q), label
+        out.append((label, poly, z, want_q, want_y))
+    return out
+
+
+def test_quotient_polynomial_bodies_on_degenerate_inputs():
+    """fr_quotient_*_body through tests/emu where the sums and differences vanish or sit at the modulus' edge"""
+    from oracle import kzg_spec as ks
+    from tests.emu import emu
+    r, n, R = ks.R, ks.FIELD_ELEMENTS_PER_BLOB, ks.FR_MONT
+    dom_m = np.frombuffer(b"".join((w * R % r).to_bytes(32, "little") for w in ks.domain_brp()), dtype=np.uint8).reshape(n, 32)
+    for label, poly, z, want_q, want_y in _degenerate_quotient_cases():
+        poly_le = np.frombuffer(b"".join(v.to_bytes(32, "little") for v in poly), dtype=np.uint8).reshape(n, 32)
+        scale = (pow(z, n, r) - 1) * pow(n, -1, r) % r
+        q, y = emu.fr_quotient("bls12_381_g1", poly_le, dom_m, np.frombuffer((z * R % r).to_bytes(32, "little"), dtype=np.uint8),
+                               np.frombuffer((scale * R % r).to_bytes(32, "little"), dtype=np.uint8), K=8)
+        assert int.from_bytes(bytes(y), "little") == want_y, label
+        assert [int.from_bytes(bytes(row), "little") for row in q] == want_q, label
+
+
+@pytest.mark.gpu
+def test_quotient_polynomial_on_device_on_degenerate_inputs():
+    """ctt_hip_fr_quotient on the same inputs"""
+    import ctypes
+
+    import torch
+    from constantine_amd import _lib
+    from oracle import kzg_spec as ks
+    L = _lib.lib()
+    r, n = ks.R, ks.FIELD_ELEMENTS_PER_BLOB
+    vp = ctypes.c_void_p
+    d_dom = torch.from_numpy(np.frombuffer(b"".join((w * ks.FR_MONT % r).to_bytes(32, "little") for w in ks.domain_brp()),
+                                           dtype=np.uint8).reshape(n, 32).copy()).cuda()
+    for label, poly, z, want_q, want_y in _degenerate_quotient_cases():
+        d_poly = torch.from_numpy(np.frombuffer(b"".join(v.to_bytes(32, "little") for v in poly), dtype=np.uint8).reshape(n, 32).copy()).cuda()
+        d_q = torch.full((n, 32), 0xA5, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        y = np.full(32, 0xA5, dtype=np.uint8)
+        zb = np.frombuffer(z.to_bytes(32, "little"), dtype=np.uint8).copy()
+        rc = L.ctt_hip_fr_quotient(None, 0, vp(d_q.data_ptr()), y.ctypes.data_as(vp), vp(d_poly.data_ptr()), vp(d_dom.data_ptr()),
+                                   zb.ctypes.data_as(vp), n)
+        assert rc == 0, label
+        assert int.from_bytes(bytes(y), "little") == want_y, label
+        assert [int.from_bytes(bytes(row), "little") for row in d_q.cpu().numpy()] == want_q, label
