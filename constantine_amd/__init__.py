@@ -9,6 +9,7 @@ Only what the MSM hot path needs lives here:
   parallel.py  point-sharded multi-GPU MSM, one process per GPU (torch.distributed / RCCL); the in-library form, one
             process driving several GPUs, is ctt_hip_msm_set_devices / $CTT_HIP_DEVICES (msm.set_devices)
   synth.py  synthetic benchmark inputs (seeded scalars)
+  verkle.py  batched Verkle commitments over a fixed Banderwagon basis: VerkleCrs.commit, batchMapToScalarField, serializeBatch_vartime
   kzg.py, evm.py  ctypes callers of the reference's KZG / EIP-2537 MSM-precompile C symbols (csrc/protocols.hip: host side in C++)
 """
 from .curves import CURVES, CurveInfo  # noqa: F401
@@ -26,3 +27,4 @@ from .msm import (  # noqa: F401
     set_devices,
     set_shard_min,
 )
+from .verkle import VerkleCrs, batchMapToScalarField, serializeBatch_vartime  # noqa: F401

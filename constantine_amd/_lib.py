@@ -6,7 +6,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CTT_MSM_HIP_LIB") or os.path.join(HERE, "libctt_msm_hip.so")
 
 _lib = None
-ABI_VERSION = 10  # ctt_hip_msm_abi_version() of the library this package was written against
+ABI_VERSION = 11  # ctt_hip_msm_abi_version() of the library this package was written against
 
 
 class HipLibraryMissing(RuntimeError):
@@ -37,7 +37,10 @@ def exported_symbols():
              "ctt_eth_kzg_compute_blob_kzg_proof", "ctt_eth_kzg_blob_to_kzg_commitment_parallel", "ctt_eth_kzg_compute_kzg_proof_parallel",
              "ctt_eth_kzg_compute_blob_kzg_proof_parallel", "ctt_eth_evm_bls12381_g1msm", "ctt_eth_evm_bls12381_g2msm",
              "ctt_hip_eth_kzg_context_from_srs", "ctt_hip_sha256", "ctt_hip_bls12_381_g1_decompress", "ctt_hip_bls12_381_g1_compress",
-             "ctt_hip_eth_kzg_blob_to_scalars", "ctt_hip_eth_kzg_challenge", "ctt_hip_eth_kzg_quotient_host"]
+             "ctt_hip_eth_kzg_blob_to_scalars", "ctt_hip_eth_kzg_challenge", "ctt_hip_eth_kzg_quotient_host",
+             # part 4: batched Verkle commitments over a fixed Banderwagon basis
+             "ctt_hip_verkle_crs_create", "ctt_hip_verkle_crs_destroy", "ctt_hip_verkle_crs_window_bits", "ctt_hip_verkle_commit_batch",
+             "ctt_hip_banderwagon_map_to_fr_batch", "ctt_hip_banderwagon_serialize_batch", "ctt_hip_verkle_last_timings"]
     return syms
 
 
@@ -222,5 +225,20 @@ def lib():
     if "ctt_hip_fr_quotient" not in missing:
         L.ctt_hip_fr_quotient.argtypes = [vp, i32, vp, vp, vp, vp, vp, u32]
         L.ctt_hip_fr_quotient.restype = i32
+    if "ctt_hip_verkle_crs_create" not in missing:
+        L.ctt_hip_verkle_crs_create.argtypes = [vp, vp, sz, i32, i32]
+        L.ctt_hip_verkle_crs_create.restype = vp
+        L.ctt_hip_verkle_crs_destroy.argtypes = [vp, vp]
+        L.ctt_hip_verkle_crs_destroy.restype = None
+        L.ctt_hip_verkle_crs_window_bits.argtypes = [vp]
+        L.ctt_hip_verkle_crs_window_bits.restype = i32
+        L.ctt_hip_verkle_commit_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, sz, i32]
+        L.ctt_hip_verkle_commit_batch.restype = i32
+        L.ctt_hip_banderwagon_map_to_fr_batch.argtypes = [vp, vp, vp, sz, i32]
+        L.ctt_hip_banderwagon_map_to_fr_batch.restype = i32
+        L.ctt_hip_banderwagon_serialize_batch.argtypes = [vp, vp, vp, sz, i32]
+        L.ctt_hip_banderwagon_serialize_batch.restype = i32
+        L.ctt_hip_verkle_last_timings.argtypes = [vp, vp, i32]
+        L.ctt_hip_verkle_last_timings.restype = i32
     _lib = L
     return L

@@ -95,6 +95,19 @@ CTT_HD void ed_madd(XYZZ<F>& acc, bool& empty, const F& qx_in, const F& qy, S ne
   const F E = F::sub(F::sub(F::mul(F::add(acc.x, acc.y), F::add(qx, qy)), A), B);
   acc = ed_add_tail<F>(A, B, C, acc.zz, E);
 }
+// acc += q, q a precomputed record (x, y, d*x*y) that already carries its sign (-q = (-x, y, -d*x*y)): 8M -- neither x*y nor the
+// multiplication by d is left to do (the fixed-base table of verkle_bodies.h).  An empty accumulator takes the record: T = x*y, 1M.
+template <class F>
+CTT_HD void ed_madd_pre(XYZZ<F>& acc, bool& empty, const F& qx, const F& qy, const F& qdt) {
+  if (empty) {
+    acc = {qx, qy, F::one(), F::mul(qx, qy)};
+    empty = false;
+    return;
+  }
+  const F A = F::mul(acc.x, qx), B = F::mul(acc.y, qy), C = F::mul(acc.zzz, qdt);
+  const F E = F::sub(F::sub(F::mul(F::add(acc.x, acc.y), F::add(qx, qy)), A), B);
+  acc = ed_add_tail<F>(A, B, C, acc.zz, E);
+}
 // 2p (dbl-2008-hwcd: 4M + 4S); Z = 1 for an affine point (mdbl)
 template <class F>
 CTT_HD XYZZ<F> ed_dbl_z(const F& X, const F& Y, const F& ZZ2) {   // ZZ2 = 2 Z^2

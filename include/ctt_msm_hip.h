@@ -382,6 +382,39 @@ void ctt_hip_eth_kzg_challenge(uint8_t z_be[32], const uint8_t* blob, const uint
 void ctt_hip_eth_kzg_quotient_host(uint8_t* q_le, uint8_t y_le[32], const uint8_t* poly_le, const uint8_t z_le[32]);
 #endif /* CTT_MSM_HIP_NO_PROTOCOLS */
 
+/* ---- Part 4: batched Verkle commitments over a fixed Banderwagon basis -----------------------------------------------------
+ * A Verkle node commits 256 scalars against the 256 points of a fixed CRS (constantine/ethereum_verkle_ipa.nim), maps the commitment
+ * to a scalar for its parent (batchMapToScalarField) and sometimes serialises it (serializeBatch_vartime,
+ * serialization/codecs_banderwagon.nim); a tree update does so thousands of times over the same points.  These symbols keep a table
+ * of precomputed multiples of the CRS on the GPU and compute many commitments in one dedicated kernel: no sort, no buckets, no
+ * tickets.  Return values as in Part 1c: 0; -1 refused (NULL crs, a crs of another context, every output NULL, a coef_kind other
+ * than CTT_HIP_COEF_BIG / _FR, an m whose buffers would pass 2^31 - 1 bytes, no device); -2 out of device memory.  Outputs are
+ * untouched on error and ctt_hip_last_error() says why.  ctx == NULL is the default context; m == 0 returns 0 and writes nothing;
+ * every call blocks, on the context's main stream, and may be made while MSM tickets are outstanding on the context.
+ *
+ * crs_create: n affine Banderwagon elements, 1 <= n <= 256 ((0, 1) and (0, -1) are legal), on the host or (on_device = 1) in HBM.
+ * window_bits 0 = the default (10), else 2 .. 10: the table holds j * 2^off(w) * P_i for every window w of the balanced layout and
+ * j = 1 .. 2^(width(w) - 1) as (x, y, d*x*y) -- 276 MiB at 10 bits and 256 points, 93 MiB at 8.  NULL on refusal (last error -1, -2 or -3).
+ * $CTT_HIP_VERKLE_PAD=1 pads the 96-byte records to 128 bytes (an experiment knob, read by crs_create).  Destroy a crs before its context. */
+typedef struct ctt_hip_verkle_crs ctt_hip_verkle_crs;
+ctt_hip_verkle_crs* ctt_hip_verkle_crs_create(ctt_hip_msm_ctx* ctx, const void* points_aff, size_t n, int window_bits, int on_device);
+void ctt_hip_verkle_crs_destroy(ctt_hip_msm_ctx* ctx, ctt_hip_verkle_crs* crs);
+int ctt_hip_verkle_crs_window_bits(const ctt_hip_verkle_crs* crs);
+/* R_k = sum_i coefs[k][i] * P_i for m rows of n scalars, row-major, 32 bytes each: CTT_HIP_COEF_BIG (canonical, any value below 2^253)
+ * or CTT_HIP_COEF_FR (Montgomery).  Any of out_prj (m x 96 bytes: (x, y, 1), byte-identical to ctt_hip_msm_banderwagon_ec_prj_* on the
+ * same row; the neutral is (0, 1, 1)), out_ser (m x 32 bytes, big-endian: x if y >= (p-1)/2 else p - x) and out_fr (m x 32 bytes:
+ * ((x / y) mod p) mod r, Montgomery) may be NULL; at least one is not.  on_device applies to coefs and to all outputs together
+ * (device buffers 4-byte aligned). */
+int ctt_hip_verkle_commit_batch(ctt_hip_msm_ctx* ctx, const ctt_hip_verkle_crs* crs, int coef_kind, void* out_prj, void* out_ser,
+                                void* out_fr, const void* coefs, size_t m, int on_device);
+/* batchMapToScalarField / serializeBatch_vartime on caller-supplied projective points (m x 96 bytes, any Z), one inversion per
+ * eight points.  The reference's inv(0) = 0: Y = 0 maps to the scalar 0, Z = 0 serialises to 32 zero bytes. */
+int ctt_hip_banderwagon_map_to_fr_batch(ctt_hip_msm_ctx* ctx, void* out_fr, const void* points_prj, size_t m, int on_device);
+int ctt_hip_banderwagon_serialize_batch(ctt_hip_msm_ctx* ctx, void* out_ser, const void* points_prj, size_t m, int on_device);
+/* HIP-event times (ms) of the context's last commit batch -- recorded while the option "timings" is non-zero -- and of its last
+ * table build: commit kernel, finish kernel, table build.  Returns 0, or -1 without a usable context. */
+int ctt_hip_verkle_last_timings(ctt_hip_msm_ctx* ctx, float* ms, int cap);
+
 #ifdef __cplusplus
 }
 #endif
