@@ -40,7 +40,7 @@ def exported_symbols():
              "ctt_hip_eth_kzg_blob_to_scalars", "ctt_hip_eth_kzg_challenge", "ctt_hip_eth_kzg_quotient_host",
              # part 4: batched Verkle commitments over a fixed Banderwagon basis
              "ctt_hip_verkle_crs_create", "ctt_hip_verkle_crs_destroy", "ctt_hip_verkle_crs_window_bits", "ctt_hip_verkle_commit_batch",
-             "ctt_hip_banderwagon_map_to_fr_batch", "ctt_hip_banderwagon_serialize_batch", "ctt_hip_verkle_last_timings"]
+             "ctt_hip_banderwagon_map_to_fr_batch", "ctt_hip_banderwagon_serialize_batch", "ctt_hip_verkle_last_timings", "ctt_hip_verkle_update_batch"]
     return syms
 
 
@@ -240,5 +240,8 @@ def lib():
         L.ctt_hip_banderwagon_serialize_batch.restype = i32
         L.ctt_hip_verkle_last_timings.argtypes = [vp, vp, i32]
         L.ctt_hip_verkle_last_timings.restype = i32
+    if "ctt_hip_verkle_update_batch" not in missing:
+        L.ctt_hip_verkle_update_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32]
+        L.ctt_hip_verkle_update_batch.restype = i32
     _lib = L
     return L

@@ -10,6 +10,8 @@ static constexpr int VK_DEFAULT_WINDOW_BITS = 10;   // measured best of 6, 8, 10
 
 void vk_launch_table(hipStream_t stream, const VkTableArgs& a);     // a.n * a.W lanes
 void vk_launch_commit(hipStream_t stream, const VkCommitArgs& a);   // a.m workgroups of VK_MAX_BASES lanes
+void vk_launch_update(hipStream_t stream, const VkUpdateArgs& a);   // ceil(a.m / 4) workgroups of 256 lanes: one wavefront per row
+void vk_launch_delta(hipStream_t stream, const VkDeltaArgs& a);     // a.m lanes
 void vk_launch_finish(hipStream_t stream, const VkFinishArgs& a);   // ceil(a.m / a.K) lanes
 
 }  // namespace ctt

@@ -9,6 +9,9 @@
 //            after window: record index = i * rows + vk_row_off(w) + j - 1.
 //   commit   lane i of a workgroup walks the Booth digits of scalar i of the row (the digits of booth_digit_packed) and adds one record
 //            per non-zero digit with ed_madd_pre (8M, ec.h); the workgroup then sums its lanes pairwise (the __global__ wrapper, verkle.hip).
+//   update   a node in service changes a few of its 256 slots: new commitment = old commitment + sum (new - old) * P_i over those slots.
+//            A row is a CSR list of (base index, delta); its entries x windows are spread over the lanes of one wave, one record per
+//            non-zero digit as above, and the lane that ends up with the sum adds the old commitment.
 //   finish   one inversion per chunk of points (Montgomery's trick over Y*Z) yields 1/Z and 1/Y of every point:
 //            (x, y, 1), serializeBatch_vartime (serialization/codecs_banderwagon.nim:239-266), batchMapToScalarField (ethereum_verkle_ipa.nim:247-281).
 //
@@ -155,6 +158,108 @@ CTT_HD void vk_store_ext(uint32_t* out, uint32_t k, const XYZZ<F>& sum) {
   vk_store<F>(o + F::N, r.y);
   vk_store<F>(o + 2 * F::N, r.zz);
   vk_store<F>(o + 3 * F::N, r.zzz);
+}
+
+// ---------------------------------------------------------------------------------------------
+// update: row k = old commitment + a few (base index, delta) entries; lane l of the row's group of G lanes
+// ---------------------------------------------------------------------------------------------
+struct VkUpdateArgs {
+  const uint32_t* tab;
+  uint32_t n, W;
+  WinLayout lay;
+  uint32_t rows, stride;
+  const uint32_t* row_ptr;   // [m + 1] first entry of every row, row_ptr[0] = 0 (CSR)
+  const uint8_t* idx;        // [row_ptr[m]] base of every entry, below n
+  const uint32_t* deltas;    // [row_ptr[m]][8]
+  int fr;                    // 1: Montgomery residues of the scalar field, converted here
+  const uint32_t* base;      // [m][24] old commitments (X, Y, Z), any non-zero Z; null: the neutral
+  uint32_t m;
+  uint32_t* out;             // [m] extended points, VK_EXT_WORDS each
+};
+
+// booth_digit_packed on a scalar held in registers, for a window that differs from lane to lane: the two words the window's bits
+// lie in are picked by a select chain over compile-time indices, so the scalar never becomes a run-time-indexed array (scratch).
+CTT_HD uint32_t vk_digit_regs(const uint32_t (&s)[8], uint32_t w, const WinLayout& L) {
+  const uint32_t i = (uint32_t)L.off(w), c = (uint32_t)L.width(w);
+  const uint32_t pos = i ? i - 1u : 0u, word = pos >> 5, sh = pos & 31u;
+  uint32_t lo = 0, hi = 0;
+#pragma unroll
+  for (int t = 0; t < 8; t++) {
+    lo = word == (uint32_t)t ? s[t] : lo;
+    if (t < 7) hi = word == (uint32_t)t ? s[t + 1] : hi;
+  }
+  uint32_t d = i ? (uint32_t)((((uint64_t)hi << 32) | lo) >> sh) : lo << 1;
+  d &= (1u << (c + 1)) - 1u;
+  const uint32_t neg = d >> c, e = (d + 1u) >> 1;
+  const uint32_t val = (neg ? (1u << c) - e : e) & ((1u << c) - 1u);
+  return val ? (((val - 1u) << 1) | neg) : DIGIT_NONE;
+}
+
+// The row's cnt * W items are (entry t / W, window t % W); lane l takes the items l, l + G, l + 2G, ... and adds one record per
+// non-zero digit.  Two entries of a row may name the same base.  A canonical scalar's digit is read from global memory where it lies
+// (booth_digit_packed); a Montgomery one is converted first, one product against the eight of the addition.
+template <class F, class Fr>
+CTT_HD XYZZ<F> vk_update_lane_sum(const VkUpdateArgs& a, uint32_t k, uint32_t l, uint32_t G) {
+  XYZZ<F> acc = XYZZ<F>::inf();
+  if (k >= a.m) return acc;
+  const uint32_t e0 = a.row_ptr[k], cnt = a.row_ptr[k + 1] - e0;
+  const uint32_t qG = G / a.W, rG = G % a.W;
+  uint32_t ent = l / a.W, w = l % a.W;
+  bool empty = true;
+  while (ent < cnt) {
+    const uint64_t e = (uint64_t)e0 + ent;
+    uint32_t dg;
+    if (a.fr) {
+      const Fr v = Fr::from_mont(vk_load<Fr>(a.deltas + e * 8));
+      uint32_t s[8];
+#pragma unroll
+      for (int t = 0; t < 8; t++) s[t] = v.l[t];
+      dg = vk_digit_regs(s, w, a.lay);
+    } else {
+      dg = booth_digit_packed(a.deltas + e * 8, (int)w, a.lay);
+    }
+    if (dg != DIGIT_NONE) {
+      const bool neg = (dg & 1u) != 0;
+      const uint32_t* rec = a.tab + ((uint64_t)a.idx[e] * a.rows + vk_row_off(a.lay, w) + (dg >> 1)) * a.stride;
+      const F x = vk_load<F>(rec), y = vk_load<F>(rec + F::N), t = vk_load<F>(rec + 2 * F::N);
+      ed_madd_pre<F>(acc, empty, F::cneg(x, neg), y, F::cneg(t, neg));
+    }
+    ent += qG;
+    w += rG;
+    if (w >= a.W) {
+      w -= a.W;
+      ent++;
+    }
+  }
+  if (empty) acc = XYZZ<F>::inf();
+  return acc;
+}
+
+// what the lane that owns the row's sum writes: old commitment + sum.  (X : Y : Z) is the extended point (XZ : YZ : Z^2 : XY).
+template <class F>
+CTT_HD void vk_update_store(const VkUpdateArgs& a, uint32_t k, XYZZ<F> sum) {
+  if (a.base) {
+    const uint32_t* b = a.base + (uint64_t)k * 24u;
+    const F X = vk_load<F>(b), Y = vk_load<F>(b + F::N), Z = vk_load<F>(b + 2 * F::N);
+    sum = ed_add<F>(sum, XYZZ<F>{F::mul(X, Z), F::mul(Y, Z), F::sqr(Z), F::mul(X, Y)});
+  }
+  vk_store_ext<F>(a.out, k, sum);
+}
+
+// the parent's delta: dfr[k] = fr[k] - base_fr[k] for the maps of the new and the old commitment (base_fr null: the old one is the
+// neutral, whose map is 0).  One lane per row; dfr may be fr itself.
+struct VkDeltaArgs {
+  const uint32_t* fr;        // [m][8] map of the new commitments, Montgomery
+  const uint32_t* base_fr;   // [m][8] map of the old ones, or null
+  uint32_t m;
+  uint32_t* dfr;             // [m][8]
+};
+template <class Fr>
+CTT_HD void vk_delta_body(const VkDeltaArgs& a, uint32_t lane) {
+  if (lane >= a.m) return;
+  Fr v = vk_load<Fr>(a.fr + (uint64_t)lane * 8u);
+  if (a.base_fr) v = Fr::sub(v, vk_load<Fr>(a.base_fr + (uint64_t)lane * 8u));
+  vk_store<Fr>(a.dfr + (uint64_t)lane * 8u, v);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -3,6 +3,10 @@ Batched Verkle commitments over a fixed Banderwagon basis (include/ctt_msm_hip.h
 
   VerkleCrs(points).commit(coefs)        m commitments of n scalars each against the n <= 256 cached points, and of every commitment
                                          the projective point, its 32-byte serialisation and its map to the scalar field
+  VerkleCrs(points).update(deltas, idx, row_ptr, base)
+                                         m sparse updates in one pass: old commitment + sum of delta * P_idx over the few changed slots
+                                         of every row (CSR: row_ptr, idx), and of every result the same outputs plus "dfr", the delta
+                                         map(new) - map(old) that the parent node takes
   batchMapToScalarField(points_prj)      constantine/ethereum_verkle_ipa.nim:247-281
   serializeBatch_vartime(points_prj)     constantine/serialization/codecs_banderwagon.nim:239-266
 
@@ -20,7 +24,8 @@ from . import _lib
 from .msm import MsmRefused
 
 _WANT = ("prj", "ser", "fr")
-_BYTES = {"prj": 96, "ser": 32, "fr": 32}
+_WANT_UPDATE = _WANT + ("dfr",)
+_BYTES = {"prj": 96, "ser": 32, "fr": 32, "dfr": 32}
 MAX_BASES = 256
 
 
@@ -115,8 +120,52 @@ class VerkleCrs:
             _refused(self.L, rc, "ctt_hip_verkle_commit_batch")
         return out
 
+    def update(self, deltas, idx, row_ptr, base=None, fr_coefs=False, want=_WANT):
+        """Row k = base[k] + sum of deltas[e] * P_idx[e] over e in [row_ptr[k], row_ptr[k + 1]): {"prj", "ser", "fr", "dfr"} (the keys of
+        `want`), "dfr" (m, 32) being map(row k) - map(base[k]) mod r in Montgomery form.  deltas (E, 32) host array or CUDA tensor,
+        base (m, 96) projective of the same kind or None (the neutral); idx (E,) and row_ptr (m + 1,) are host integers.  Entries of a
+        row may repeat a base; a row may be empty.  No dispatch to commit() happens here, however long the rows are."""
+        want = tuple(want)
+        if not want or any(w not in _WANT_UPDATE for w in want):
+            raise ValueError(f"want is a non-empty subset of {_WANT_UPDATE}")
+        deltas = _shaped(deltas, (32,), "deltas")
+        E = int(deltas.shape[0])
+        idx, row_ptr = np.asarray(idx), np.asarray(row_ptr)
+        if idx.ndim != 1 or idx.shape[0] != E or (E and idx.dtype.kind not in "iu"):
+            raise ValueError("idx is one integer per row of deltas")
+        if row_ptr.ndim != 1 or row_ptr.shape[0] < 1 or (row_ptr.dtype.kind not in "iu"):
+            raise ValueError("row_ptr is (m + 1,) integers")
+        m = int(row_ptr.shape[0]) - 1
+        if int(row_ptr[0]) != 0 or int(row_ptr[-1]) != E or (m and bool(np.any(np.diff(row_ptr.astype(np.int64)) < 0))):
+            raise ValueError("row_ptr rises monotonically from 0 to the number of entries")
+        if E and (int(idx.min()) < 0 or int(idx.max()) >= self.n):
+            raise ValueError(f"idx holds indices in [0, {self.n})")
+        if base is not None:
+            if _is_cuda(base) != _is_cuda(deltas):
+                raise ValueError("base and deltas are both host arrays or both CUDA tensors")
+            base = _shaped(base, (96,), "base")
+            if int(base.shape[0]) != m:
+                raise ValueError(f"base has {int(base.shape[0])} rows, row_ptr {m}")
+            if _is_cuda(base) and base.device != deltas.device:
+                raise ValueError("base and deltas are on different devices")
+        if not self.handle:
+            raise ValueError("this VerkleCrs is closed")
+        idx = np.ascontiguousarray(idx, dtype=np.uint8)
+        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.uint32)
+        out = {w: _empty_like(deltas, m, _BYTES[w]) for w in _WANT_UPDATE if w in want}
+        if m == 0:
+            return out
+        _order(self.L, self.ctx, deltas)
+        _order(self.L, self.ctx, base)
+        rc = self.L.ctt_hip_verkle_update_batch(self.ctx, self.handle, 1 if fr_coefs else 0, _ptr(out.get("prj")), _ptr(out.get("ser")),
+                                                _ptr(out.get("fr")), _ptr(out.get("dfr")), _ptr(base), _ptr(row_ptr), _ptr(idx),
+                                                _ptr(deltas), m, 1 if _is_cuda(deltas) else 0)
+        if rc != 0:
+            _refused(self.L, rc, "ctt_hip_verkle_update_batch")
+        return out
+
     def last_timings(self):
-        """ms of the context's last commit batch (after DeviceMsm.enable_timings) and of its last table build"""
+        """ms of the context's last commit (or update) batch (after DeviceMsm.enable_timings) and of its last table build"""
         ms = np.zeros(3, dtype=np.float32)
         self.L.ctt_hip_verkle_last_timings(self.ctx, ms.ctypes.data_as(ctypes.c_void_p), 3)
         return dict(zip(("commit", "finish", "table"), (float(x) for x in ms)))

@@ -411,8 +411,20 @@ int ctt_hip_verkle_commit_batch(ctt_hip_msm_ctx* ctx, const ctt_hip_verkle_crs* 
  * eight points.  The reference's inv(0) = 0: Y = 0 maps to the scalar 0, Z = 0 serialises to 32 zero bytes. */
 int ctt_hip_banderwagon_map_to_fr_batch(ctt_hip_msm_ctx* ctx, void* out_fr, const void* points_prj, size_t m, int on_device);
 int ctt_hip_banderwagon_serialize_batch(ctt_hip_msm_ctx* ctx, void* out_ser, const void* points_prj, size_t m, int on_device);
-/* HIP-event times (ms) of the context's last commit batch -- recorded while the option "timings" is non-zero -- and of its last
- * table build: commit kernel, finish kernel, table build.  Returns 0, or -1 without a usable context. */
+/* The sparse update of m commitments: R_k = base_k + sum over e in [row_ptr[k], row_ptr[k+1]) of deltas[e] * P_idx[e] -- what a tree in
+ * service does to a node of which a block changed a few slots (deltas = new - old value, mod r), in one pass: one wavefront per row,
+ * the row's entries x windows spread over its lanes.  row_ptr (m + 1 values, CSR) and idx (row_ptr[m] bytes) are ALWAYS host memory
+ * and are checked before anything is launched: row_ptr[0] == 0, non-decreasing, every idx[e] < n of the crs, row_ptr[m] * 32 and every
+ * m-sized buffer below 2^31 - 1 bytes (else -1, outputs untouched).  Two entries of a row may name the same base; a row may be empty.
+ * deltas: row_ptr[m] x 32 bytes, CTT_HIP_COEF_BIG or _FR as above.  base_prj: m x 96 bytes (X, Y, Z) Montgomery, any non-zero Z, or NULL
+ * for the neutral.  out_prj, out_ser, out_fr as for commit_batch; out_dfr (m x 32 bytes, Montgomery) = map(R_k) - map(base_k) mod r, the
+ * delta the parent node takes for this child (map(neutral) = 0).  Any output may be NULL; at least one is not.  on_device applies to
+ * deltas, base_prj and all four outputs together.  ctt_hip_verkle_last_timings then reports the update kernel and the finish. */
+int ctt_hip_verkle_update_batch(ctt_hip_msm_ctx* ctx, const ctt_hip_verkle_crs* crs, int coef_kind, void* out_prj, void* out_ser,
+                                void* out_fr, void* out_dfr, const void* base_prj, const uint32_t* row_ptr, const uint8_t* idx,
+                                const void* deltas, size_t m, int on_device);
+/* HIP-event times (ms) of the context's last commit or update batch -- recorded while the option "timings" is non-zero -- and of its
+ * last table build: commit (update) kernel, finish kernel(s), table build.  Returns 0, or -1 without a usable context. */
 int ctt_hip_verkle_last_timings(ctt_hip_msm_ctx* ctx, float* ms, int cap);
 
 #ifdef __cplusplus
