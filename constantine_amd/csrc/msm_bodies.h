@@ -87,21 +87,19 @@ CTT_HD WinLayout window_layout(int bits, int c, int* W) {
   return L;
 }
 
-// digit of window w -> packed ((val-1)<<1 | neg) or DIGIT_NONE when val == 0 (Booth signed digits, bigints.nim:806-859, over
-// the window's own width)
+// d = (the c bits of a window) << 1 | the bit below it -> packed ((val-1)<<1 | neg) or DIGIT_NONE when val == 0 (Booth signed
+// digits, bigints.nim:806-859, over the window's own width)
+CTT_HD uint32_t booth_recode_packed(uint32_t d, uint32_t c) {
+  const uint32_t neg = d >> c, e = (d + 1u) >> 1;
+  const uint32_t val = (neg ? (1u << c) - e : e) & ((1u << c) - 1u);
+  return val ? (((val - 1u) << 1) | neg) : DIGIT_NONE;
+}
+
+// packed digit of window w of the scalar k in memory
 CTT_HD uint32_t booth_digit_packed(const uint32_t* k, int w, const WinLayout& L) {
   const int i = L.off((uint32_t)w), c = L.width((uint32_t)w);
-  uint32_t d;
-  if (i == 0) {
-    d = (k[0] << 1) & ((1u << (c + 1)) - 1u);
-  } else {
-    d = scalar_bits_at(k, i - 1, c + 1);
-  }
-  uint32_t neg = d >> c;
-  uint32_t e = (d + 1u) >> 1;
-  uint32_t val = neg ? (1u << c) - e : e;
-  val &= (1u << c) - 1u;
-  return val ? (((val - 1u) << 1) | neg) : DIGIT_NONE;
+  const uint32_t d = i == 0 ? (k[0] << 1) & ((1u << (c + 1)) - 1u) : scalar_bits_at(k, i - 1, c + 1);
+  return booth_recode_packed(d, (uint32_t)c);
 }
 
 // The digits of windows [w0, w0 + nw) of NS scalars held in registers, window by window: fn(w, d[NS]) with the packed digit

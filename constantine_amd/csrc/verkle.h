@@ -1,4 +1,5 @@
-// verkle.h -- launchers of the batched Verkle commitment kernels (verkle.hip) for the engine's C ABI (msm_engine.hip).
+// verkle.h -- launchers of the batched Verkle commitment and update kernels (verkle.hip) for the engine's C ABI (msm_engine.hip).  The
+// table, commit and update arguments each begin with the VkTable view of the CRS handle (verkle_bodies.h).
 #pragma once
 #include <hip/hip_runtime.h>
 

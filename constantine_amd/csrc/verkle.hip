@@ -1,4 +1,5 @@
-// verkle.hip -- kernels of the batched Verkle commitment over a fixed Banderwagon basis (bodies: verkle_bodies.h).
+// verkle.hip -- kernels of the batched Verkle commitment and update over a fixed Banderwagon basis (bodies: verkle_bodies.h, DESIGN.md
+// sections 11 and 12).  The commit and the update kernel share the LDS tree vk_tree.
 #include "verkle.h"
 
 #include "hip_errors.h"
@@ -27,82 +28,40 @@ __global__ void __launch_bounds__(VK_TABLE_BLOCK) k_vk_table(VkTableArgs a) {
   vk_table_body<VkF>(a, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
-// One workgroup per commitment, lane i owns base i: W gathers and mixed additions in registers, then the lanes are summed pairwise
-// through LDS -- in every step the upper half of the live lanes hands its point to the lower half (128 slots of 128 bytes, stored
-// word-major so that a wave's accesses fall into consecutive banks).  Lanes without a base or without a non-zero digit hold the
-// in-memory neutral, which ed_add passes through.
+// The pairwise sum of a group of lanes through its SLOTS slots of LDS (vk_tree_put / vk_tree_take, verkle_bodies.h), from level `first`
+// down to 1: afterwards lane 0 holds the sum of the lanes below 2 * first.  Every lane of the workgroup runs the same levels, so
+// the barriers are uniform.
+template <uint32_t SLOTS>
+__device__ __forceinline__ void vk_tree(uint32_t* slots, uint32_t lane, uint32_t first, XYZZ<VkF>& acc) {
+#pragma unroll 1
+  for (uint32_t s = first; s >= 1; s >>= 1) {
+    vk_tree_put<VkF, SLOTS>(slots, lane, s, acc);
+    __syncthreads();
+    vk_tree_take<VkF, SLOTS>(slots, lane, s, acc);
+    __syncthreads();
+  }
+}
+
+// One workgroup per commitment, lane i owns base i: W gathers and mixed additions in registers, then the tree over the live lanes
+// (128 slots of 128 bytes).  Lanes without a base or without a non-zero digit hold the in-memory neutral.
 __global__ void __launch_bounds__(VK_MAX_BASES) k_vk_commit(VkCommitArgs a) {
   __shared__ uint32_t slots[VK_EXT_WORDS * VK_TREE_SLOTS];
   const uint32_t k = blockIdx.x, lane = threadIdx.x;
   XYZZ<VkF> acc = vk_lane_sum<VkF, VkFr>(a, k, lane);
   uint32_t live = 1;
   while (live < a.n) live <<= 1;
-#pragma unroll 1
-  for (uint32_t s = live >> 1; s >= 1; s >>= 1) {
-    if (lane >= s && lane < 2 * s) {
-      uint32_t* o = slots + (lane - s);
-#pragma unroll
-      for (int t = 0; t < 8; t++) {
-        o[t * VK_TREE_SLOTS] = acc.x.l[t];
-        o[(8 + t) * VK_TREE_SLOTS] = acc.y.l[t];
-        o[(16 + t) * VK_TREE_SLOTS] = acc.zz.l[t];
-        o[(24 + t) * VK_TREE_SLOTS] = acc.zzz.l[t];
-      }
-    }
-    __syncthreads();
-    if (lane < s) {
-      const uint32_t* o = slots + lane;
-      XYZZ<VkF> q;
-#pragma unroll
-      for (int t = 0; t < 8; t++) {
-        q.x.l[t] = o[t * VK_TREE_SLOTS];
-        q.y.l[t] = o[(8 + t) * VK_TREE_SLOTS];
-        q.zz.l[t] = o[(16 + t) * VK_TREE_SLOTS];
-        q.zzz.l[t] = o[(24 + t) * VK_TREE_SLOTS];
-      }
-      acc = ed_add<VkF>(acc, q);
-    }
-    __syncthreads();
-  }
+  vk_tree<VK_TREE_SLOTS>(slots, lane, live >> 1, acc);
   if (lane == 0) vk_store_ext<VkF>(a.out, k, acc);
 }
 
-// One wavefront per row, four rows per workgroup: the lanes of a wave share the row's entries x windows (vk_update_lane_sum), then six
-// ed_add levels through the wave's own 32 slots of LDS, word-major as above.  Every wave runs the same six levels, so the barriers
-// are uniform; a wave without a row loads nothing and holds neutrals.
+// One wavefront per row, four rows per workgroup: the lanes of a wave share the row's entries x windows (vk_update_lane_sum), then the
+// six levels of the tree through the wave's own 32 slots.  A wave without a row loads nothing and holds neutrals.
 __global__ void __launch_bounds__(VK_UPDATE_BLOCK) k_vk_update(VkUpdateArgs a) {
   __shared__ uint32_t slots[VK_UPDATE_ROWS * VK_EXT_WORDS * VK_UPDATE_SLOTS];
   const uint32_t wave = threadIdx.x / VK_UPDATE_G, lane = threadIdx.x % VK_UPDATE_G;
   const uint32_t k = blockIdx.x * VK_UPDATE_ROWS + wave;
   XYZZ<VkF> acc = vk_update_lane_sum<VkF, VkFr>(a, k, lane, VK_UPDATE_G);
-  uint32_t* mine = slots + wave * (VK_EXT_WORDS * VK_UPDATE_SLOTS);
-#pragma unroll 1
-  for (uint32_t s = VK_UPDATE_SLOTS; s >= 1; s >>= 1) {
-    if (lane >= s && lane < 2 * s) {
-      uint32_t* o = mine + (lane - s);
-#pragma unroll
-      for (int t = 0; t < 8; t++) {
-        o[t * VK_UPDATE_SLOTS] = acc.x.l[t];
-        o[(8 + t) * VK_UPDATE_SLOTS] = acc.y.l[t];
-        o[(16 + t) * VK_UPDATE_SLOTS] = acc.zz.l[t];
-        o[(24 + t) * VK_UPDATE_SLOTS] = acc.zzz.l[t];
-      }
-    }
-    __syncthreads();
-    if (lane < s) {
-      const uint32_t* o = mine + lane;
-      XYZZ<VkF> q;
-#pragma unroll
-      for (int t = 0; t < 8; t++) {
-        q.x.l[t] = o[t * VK_UPDATE_SLOTS];
-        q.y.l[t] = o[(8 + t) * VK_UPDATE_SLOTS];
-        q.zz.l[t] = o[(16 + t) * VK_UPDATE_SLOTS];
-        q.zzz.l[t] = o[(24 + t) * VK_UPDATE_SLOTS];
-      }
-      acc = ed_add<VkF>(acc, q);
-    }
-    __syncthreads();
-  }
+  vk_tree<VK_UPDATE_SLOTS>(slots + wave * (VK_EXT_WORDS * VK_UPDATE_SLOTS), lane, VK_UPDATE_SLOTS, acc);
   if (lane == 0 && k < a.m) vk_update_store<VkF>(a, k, acc);
 }
 

@@ -7,11 +7,14 @@
 //   table    for base i, window w of the balanced layout (msm_bodies.h window_layout) and j = 1 .. 2^(width(w)-1) the record
 //            (x, y, d*x*y) of j * 2^off(w) * P_i, affine.  -(x, y, t) = (-x, y, -t).  All records of a base are consecutive, window
 //            after window: record index = i * rows + vk_row_off(w) + j - 1.
-//   commit   lane i of a workgroup walks the Booth digits of scalar i of the row (the digits of booth_digit_packed) and adds one record
-//            per non-zero digit with ed_madd_pre (8M, ec.h); the workgroup then sums its lanes pairwise (the __global__ wrapper, verkle.hip).
+//            VkTable is the view of it that every kernel's arguments hold and the one place a record's address is computed.
+//   commit   lane i of a workgroup walks the Booth digits of scalar i of the row (booth_recode_packed, msm_bodies.h) and adds one record
+//            per non-zero digit (vk_add_record: ed_madd_pre, 8M, ec.h); the workgroup then sums its lanes pairwise (the tree below).
 //   update   a node in service changes a few of its 256 slots: new commitment = old commitment + sum (new - old) * P_i over those slots.
 //            A row is a CSR list of (base index, delta); its entries x windows are spread over the lanes of one wave, one record per
 //            non-zero digit as above, and the lane that ends up with the sum adds the old commitment.
+//   tree     the pairwise sum of a group of lanes through slots of LDS, one level in two halves (vk_tree_put, vk_tree_take) with a
+//            barrier after each; the commit kernel runs it over 128 slots, the update kernel over 32 per wave (vk_tree, verkle.hip).
 //   finish   one inversion per chunk of points (Montgomery's trick over Y*Z) yields 1/Z and 1/Y of every point:
 //            (x, y, 1), serializeBatch_vartime (serialization/codecs_banderwagon.nim:239-266), batchMapToScalarField (ethereum_verkle_ipa.nim:247-281).
 //
@@ -32,6 +35,19 @@ CTT_HD uint32_t vk_row_off(const WinLayout& L, uint32_t w) {
   return w < r ? w * wide : r * wide + (w - r) * narrow;
 }
 
+// The table as its users see it.  rec(i, w, j) is the record of (j + 1) * 2^off(w) * P_i; a walk over the windows of one base keeps
+// the running vk_row_off itself and asks with rec_at.  The arguments of the table, commit and update kernels are this view (their
+// base) followed by their own fields.
+struct VkTable {
+  uint32_t* tab;    // [n][rows] records
+  uint32_t n, W;
+  WinLayout lay;
+  uint32_t rows;    // records per base = vk_row_off(lay, W)
+  uint32_t stride;  // words per record: VK_REC_WORDS, or 32 (one 128-byte line per gather)
+  CTT_HD uint32_t* rec_at(uint32_t i, uint32_t row_off, uint32_t j) const { return tab + ((uint64_t)i * rows + row_off + j) * stride; }
+  CTT_HD uint32_t* rec(uint32_t i, uint32_t w, uint32_t j) const { return rec_at(i, vk_row_off(lay, w), j); }
+};
+
 template <class F>
 CTT_HD F vk_load(const uint32_t* p) {
   F r;
@@ -48,13 +64,8 @@ CTT_HD void vk_store(uint32_t* p, const F& v) {
 // ---------------------------------------------------------------------------------------------
 // table: one lane per (base, window)
 // ---------------------------------------------------------------------------------------------
-struct VkTableArgs {
+struct VkTableArgs : VkTable {
   const uint32_t* pts;   // [n] affine points, C-API layout (x, y Montgomery)
-  uint32_t n, W;
-  WinLayout lay;
-  uint32_t rows;         // records per base = vk_row_off(W)
-  uint32_t stride;       // words per record: VK_REC_WORDS, or 32 (one 128-byte line per gather)
-  uint32_t* tab;         // [n][rows] records
   uint32_t* pre;         // [n][rows][F::N] prefix products of Z while the lane's records are normalised
 };
 
@@ -68,12 +79,13 @@ CTT_HD void vk_table_body(const VkTableArgs& a, uint32_t lane) {
   XYZZ<F> q = {px, py, F::one(), F::mul(px, py)};
   for (int b = a.lay.off(w); b > 0; b--) q = ed_dbl<F>(q);
   const uint32_t half = 1u << (a.lay.width(w) - 1);
-  const uint64_t e0 = (uint64_t)i * a.rows + vk_row_off(a.lay, w);
+  const uint32_t row = vk_row_off(a.lay, w);
+  const uint64_t e0 = (uint64_t)i * a.rows + row;   // the lane's first record, and first prefix product
   XYZZ<F> r = XYZZ<F>::inf();
   F run = F::one();
   for (uint32_t j = 0; j < half; j++) {
     r = ed_add<F>(r, q);
-    uint32_t* rec = a.tab + (e0 + j) * a.stride;
+    uint32_t* rec = a.rec_at(i, row, j);
     vk_store<F>(rec, r.x);
     vk_store<F>(rec + F::N, r.y);
     vk_store<F>(rec + 2 * F::N, r.zz);
@@ -83,7 +95,7 @@ CTT_HD void vk_table_body(const VkTableArgs& a, uint32_t lane) {
   F inv = F::inv(run);
   const F d = ed_d<F>();
   for (uint32_t j = half; j-- > 0;) {
-    uint32_t* rec = a.tab + (e0 + j) * a.stride;
+    uint32_t* rec = a.rec_at(i, row, j);
     const F Z = vk_load<F>(rec + 2 * F::N);
     F x = F::zero(), y = F::zero();
     if (!Z.is_zero()) {   // (never zero for Banderwagon elements: the law is complete on them)
@@ -101,20 +113,23 @@ CTT_HD void vk_table_body(const VkTableArgs& a, uint32_t lane) {
 // ---------------------------------------------------------------------------------------------
 // commit: lane i of row k
 // ---------------------------------------------------------------------------------------------
-struct VkCommitArgs {
-  const uint32_t* tab;
-  uint32_t n, W;
-  WinLayout lay;
-  uint32_t rows, stride;
+struct VkCommitArgs : VkTable {
   const uint32_t* coefs;   // [m][n][8]
   uint32_t m;
   int fr;                  // 1: Montgomery residues of the scalar field, converted here
   uint32_t* out;           // [m] extended points, VK_EXT_WORDS each
 };
 
+// acc += (neg ? -1 : 1) * the record (x, y, d*x*y) at rec
+template <class F>
+CTT_HD void vk_add_record(XYZZ<F>& acc, bool& empty, const uint32_t* rec, bool neg) {
+  const F x = vk_load<F>(rec), y = vk_load<F>(rec + F::N), t = vk_load<F>(rec + 2 * F::N);
+  ed_madd_pre<F>(acc, empty, F::cneg(x, neg), y, F::cneg(t, neg));
+}
+
 // a[k][i] * P_i, or the in-memory neutral (all zero) when no digit is non-zero.  The scalar is shifted down window by window, so its
 // words are only ever addressed with compile-time indices and the addition exists once in the code; the digit of a window is
-// (its bits << 1 | the bit below) recoded as in booth_digit_packed.
+// (its bits << 1 | the bit below) recoded by booth_recode_packed.
 template <class F, class Fr>
 CTT_HD XYZZ<F> vk_lane_sum(const VkCommitArgs& a, uint32_t k, uint32_t i) {
   XYZZ<F> acc = XYZZ<F>::inf();
@@ -126,7 +141,6 @@ CTT_HD XYZZ<F> vk_lane_sum(const VkCommitArgs& a, uint32_t k, uint32_t i) {
 #pragma unroll
     for (int t = 0; t < 8; t++) s[t] = v.l[t];
   }
-  const uint32_t* base = a.tab + (uint64_t)i * a.rows * a.stride;
   bool empty = true;
   uint32_t below = 0, row = 0;
   for (uint32_t w = 0; w < a.W; w++) {
@@ -136,13 +150,8 @@ CTT_HD XYZZ<F> vk_lane_sum(const VkCommitArgs& a, uint32_t k, uint32_t i) {
 #pragma unroll
     for (int t = 0; t < 7; t++) s[t] = (s[t] >> c) | (s[t + 1] << (32u - c));
     s[7] >>= c;
-    const uint32_t neg = d >> c, e = (d + 1u) >> 1;
-    const uint32_t val = (neg ? (1u << c) - e : e) & vmask;
-    if (val) {
-      const uint32_t* rec = base + (uint64_t)(row + val - 1u) * a.stride;
-      const F x = vk_load<F>(rec), y = vk_load<F>(rec + F::N), t = vk_load<F>(rec + 2 * F::N);
-      ed_madd_pre<F>(acc, empty, F::cneg(x, neg != 0), y, F::cneg(t, neg != 0));
-    }
+    const uint32_t dg = booth_recode_packed(d, c);
+    if (dg != DIGIT_NONE) vk_add_record<F>(acc, empty, a.rec_at(i, row, dg >> 1), (dg & 1u) != 0);
     row += 1u << (c - 1);
   }
   if (empty) acc = XYZZ<F>::inf();
@@ -163,11 +172,7 @@ CTT_HD void vk_store_ext(uint32_t* out, uint32_t k, const XYZZ<F>& sum) {
 // ---------------------------------------------------------------------------------------------
 // update: row k = old commitment + a few (base index, delta) entries; lane l of the row's group of G lanes
 // ---------------------------------------------------------------------------------------------
-struct VkUpdateArgs {
-  const uint32_t* tab;
-  uint32_t n, W;
-  WinLayout lay;
-  uint32_t rows, stride;
+struct VkUpdateArgs : VkTable {
   const uint32_t* row_ptr;   // [m + 1] first entry of every row, row_ptr[0] = 0 (CSR)
   const uint8_t* idx;        // [row_ptr[m]] base of every entry, below n
   const uint32_t* deltas;    // [row_ptr[m]][8]
@@ -189,10 +194,7 @@ CTT_HD uint32_t vk_digit_regs(const uint32_t (&s)[8], uint32_t w, const WinLayou
     if (t < 7) hi = word == (uint32_t)t ? s[t + 1] : hi;
   }
   uint32_t d = i ? (uint32_t)((((uint64_t)hi << 32) | lo) >> sh) : lo << 1;
-  d &= (1u << (c + 1)) - 1u;
-  const uint32_t neg = d >> c, e = (d + 1u) >> 1;
-  const uint32_t val = (neg ? (1u << c) - e : e) & ((1u << c) - 1u);
-  return val ? (((val - 1u) << 1) | neg) : DIGIT_NONE;
+  return booth_recode_packed(d & ((1u << (c + 1)) - 1u), c);
 }
 
 // The row's cnt * W items are (entry t / W, window t % W); lane l takes the items l, l + G, l + 2G, ... and adds one record per
@@ -218,12 +220,7 @@ CTT_HD XYZZ<F> vk_update_lane_sum(const VkUpdateArgs& a, uint32_t k, uint32_t l,
     } else {
       dg = booth_digit_packed(a.deltas + e * 8, (int)w, a.lay);
     }
-    if (dg != DIGIT_NONE) {
-      const bool neg = (dg & 1u) != 0;
-      const uint32_t* rec = a.tab + ((uint64_t)a.idx[e] * a.rows + vk_row_off(a.lay, w) + (dg >> 1)) * a.stride;
-      const F x = vk_load<F>(rec), y = vk_load<F>(rec + F::N), t = vk_load<F>(rec + 2 * F::N);
-      ed_madd_pre<F>(acc, empty, F::cneg(x, neg), y, F::cneg(t, neg));
-    }
+    if (dg != DIGIT_NONE) vk_add_record<F>(acc, empty, a.rec(a.idx[e], w, dg >> 1), (dg & 1u) != 0);
     ent += qG;
     w += rG;
     if (w >= a.W) {
@@ -244,6 +241,40 @@ CTT_HD void vk_update_store(const VkUpdateArgs& a, uint32_t k, XYZZ<F> sum) {
     sum = ed_add<F>(sum, XYZZ<F>{F::mul(X, Z), F::mul(Y, Z), F::sqr(Z), F::mul(X, Y)});
   }
   vk_store_ext<F>(a.out, k, sum);
+}
+
+// ---------------------------------------------------------------------------------------------
+// tree: one level of the pairwise sum of a group of lanes through SLOTS slots of VK_EXT_WORDS words (LDS on the device, any array on
+// the CPU).  At level s the lanes s <= lane < 2s put their point into slot lane - s, then -- after a barrier -- the lanes below s take
+// slot `lane` and add it; a second barrier frees the slots for level s / 2.  A slot is stored word-major (word t of slot j at
+// t * SLOTS + j) so that a wave's accesses fall into consecutive banks; SLOTS is a template argument so that the strides are immediates.
+// The in-memory neutral passes through ed_add.
+// ---------------------------------------------------------------------------------------------
+template <class F, uint32_t SLOTS>
+CTT_HD void vk_tree_put(uint32_t* slots, uint32_t lane, uint32_t s, const XYZZ<F>& acc) {
+  if (lane < s || lane >= 2 * s) return;
+  uint32_t* o = slots + (lane - s);
+#pragma unroll
+  for (int t = 0; t < F::N; t++) {
+    o[t * SLOTS] = acc.x.l[t];
+    o[(F::N + t) * SLOTS] = acc.y.l[t];
+    o[(2 * F::N + t) * SLOTS] = acc.zz.l[t];
+    o[(3 * F::N + t) * SLOTS] = acc.zzz.l[t];
+  }
+}
+template <class F, uint32_t SLOTS>
+CTT_HD void vk_tree_take(const uint32_t* slots, uint32_t lane, uint32_t s, XYZZ<F>& acc) {
+  if (lane >= s) return;
+  const uint32_t* o = slots + lane;
+  XYZZ<F> q;
+#pragma unroll
+  for (int t = 0; t < F::N; t++) {
+    q.x.l[t] = o[t * SLOTS];
+    q.y.l[t] = o[(F::N + t) * SLOTS];
+    q.zz.l[t] = o[(2 * F::N + t) * SLOTS];
+    q.zzz.l[t] = o[(3 * F::N + t) * SLOTS];
+  }
+  acc = ed_add<F>(acc, q);
 }
 
 // the parent's delta: dfr[k] = fr[k] - base_fr[k] for the maps of the new and the old commitment (base_fr null: the old one is the

@@ -1,117 +1,24 @@
-"""Batched Verkle commitments without a GPU: the bodies of csrc/verkle_bodies.h (table, commit lane, finish) and ed_madd_pre of csrc/ec.h
-compiled for the CPU and run lane by lane against the Python-integer oracle and the reference's vectors, and the wiring of the new C ABI
+"""Batched Verkle commitments without a GPU: the bodies of csrc/verkle_bodies.h (table, commit lane, the tree through its slots, finish)
+and ed_madd_pre of csrc/ec.h compiled for the CPU (tests/verkle_harness.cpp) and run lane by lane against the Python-integer oracle and the reference's vectors, and the wiring of the new C ABI
 (include/ctt_msm_hip.h part 4) on a box without a device."""
 import ctypes
 import json
 import os
 import random
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import _banderwagon as bw
-from tests._verkle import HALF, crafted_triples, expected_finish, fr_from, layout, map_fr, rec_bytes
+from tests._verkle import build_harness, crafted_triples, expected_finish, fr_from, layout, map_fr, rec_bytes
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "constantine_amd")
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-
-HARNESS = r'''
-#include <cstdio>
-#include <cstring>
-#include <vector>
-#include "verkle_bodies.h"
-using namespace ctt;
-using F = Banderwagon::F;
-using Fr = Banderwagon::Fr;
-template <class T> static bool rd(T* p, size_t n) { return fread(p, sizeof(T), n, stdin) == n; }
-static void wr(const void* p, size_t bytes) { fwrite(p, 1, bytes, stdout); }
-struct Table {
-  VkTableArgs a;
-  std::vector<uint32_t> pts, tab, pre;
-  void build(uint32_t n, int c) {
-    int W;
-    a.lay = window_layout(Banderwagon::BITS, c, &W);
-    a.n = n; a.W = (uint32_t)W; a.rows = vk_row_off(a.lay, a.W); a.stride = VK_REC_WORDS;
-    tab.assign((size_t)n * a.rows * a.stride, 0xA5A5A5A5u);
-    pre.assign((size_t)n * a.rows * 8, 0);
-    a.pts = pts.data(); a.tab = tab.data(); a.pre = pre.data();
-    for (uint32_t lane = 0; lane < n * a.W + 3; lane++) vk_table_body<F>(a, lane);   // (three lanes past the end: they must do nothing)
-  }
-};
-static void finish(const uint32_t* src, uint32_t stride, uint32_t m, uint32_t K, uint32_t mask) {
-  std::vector<uint32_t> prj((size_t)m * 24, 0x5A5A5A5Au), ser((size_t)m * 8, 0x5A5A5A5Au), fr((size_t)m * 8, 0x5A5A5A5Au);
-  VkFinishArgs f{src, stride, m, K, (mask & 1) ? prj.data() : nullptr, (mask & 2) ? ser.data() : nullptr, (mask & 4) ? fr.data() : nullptr};
-  for (uint32_t lane = 0; lane < (m + K - 1) / K + 2; lane++) vk_finish_body<F, Fr>(f, lane);
-  wr(prj.data(), prj.size() * 4); wr(ser.data(), ser.size() * 4); wr(fr.data(), fr.size() * 4);
-}
-int main(int argc, char** argv) {
-  if (argc < 2) return 2;
-  if (!strcmp(argv[1], "table")) {          // in: n, c, n points.  out: W, rows, the table
-    uint32_t n, c;
-    Table t;
-    if (!rd(&n, 1) || !rd(&c, 1)) return 1;
-    t.pts.resize(n * 16);
-    if (!rd(t.pts.data(), n * 16)) return 1;
-    t.build(n, (int)c);
-    wr(&t.a.W, 4); wr(&t.a.rows, 4); wr(t.tab.data(), t.tab.size() * 4);
-  } else if (!strcmp(argv[1], "madd")) {    // in: count, count records (x, y, d*x*y).  out: the accumulator after every addition
-    uint32_t cnt;
-    if (!rd(&cnt, 1)) return 1;
-    XYZZ<F> acc = XYZZ<F>::inf();
-    bool empty = true;
-    for (uint32_t i = 0; i < cnt; i++) {
-      F q[3];
-      if (!rd(q, 3)) return 1;
-      ed_madd_pre<F>(acc, empty, q[0], q[1], q[2]);
-      wr(&acc, sizeof(acc));
-    }
-  } else if (!strcmp(argv[1], "commit")) {  // in: n, c, fr, m, n points, m rows of n scalars.  out: per row prj, then ser, then fr
-    uint32_t n, c, fr, m;
-    Table t;
-    if (!rd(&n, 1) || !rd(&c, 1) || !rd(&fr, 1) || !rd(&m, 1)) return 1;
-    t.pts.resize(n * 16);
-    std::vector<uint32_t> coefs((size_t)m * n * 8), ext((size_t)m * VK_EXT_WORDS);
-    if (!rd(t.pts.data(), n * 16) || !rd(coefs.data(), coefs.size())) return 1;
-    t.build(n, (int)c);
-    VkCommitArgs a{t.tab.data(), n, t.a.W, t.a.lay, t.a.rows, t.a.stride, coefs.data(), m, (int)fr, ext.data()};
-    for (uint32_t k = 0; k < m; k++) {
-      std::vector<XYZZ<F>> lanes(VK_MAX_BASES);
-      for (uint32_t i = 0; i < VK_MAX_BASES; i++) lanes[i] = vk_lane_sum<F, Fr>(a, k, i);
-      uint32_t live = 1;
-      while (live < n) live <<= 1;
-      for (uint32_t s = live >> 1; s >= 1; s >>= 1)     // the kernel's tree: the upper half of the live lanes hands over to the lower half
-        for (uint32_t l = 0; l < s; l++) lanes[l] = ed_add<F>(lanes[l], lanes[l + s]);
-      vk_store_ext<F>(a.out, k, lanes[0]);
-    }
-    finish(ext.data(), VK_EXT_WORDS, m, VK_FINISH_CHUNK, 7);
-  } else if (!strcmp(argv[1], "finish")) {  // in: m, K, mask, m points (X, Y, Z).  out: prj, ser, fr (0x5A where not requested)
-    uint32_t m, K, mask;
-    if (!rd(&m, 1) || !rd(&K, 1) || !rd(&mask, 1)) return 1;
-    std::vector<uint32_t> src((size_t)m * 24);
-    if (!rd(src.data(), src.size())) return 1;
-    finish(src.data(), 24, m, K, mask);
-  } else {
-    return 2;
-  }
-  return 0;
-}
-'''
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    d = tmp_path_factory.mktemp("verkle")
-    cxx = shutil.which("g++") or shutil.which("c++")
-    (d / "vk.cpp").write_text(HARNESS)
-    subprocess.run([cxx, "-O2", "-std=c++17", "-I", os.path.join(PKG, "csrc"), str(d / "vk.cpp"), "-o", str(d / "vk")], check=True)
-
-    def run(mode, data):
-        return subprocess.run([str(d / "vk"), mode], input=data, check=True, capture_output=True).stdout
-    return run
+    return build_harness(tmp_path_factory.mktemp("verkle"))
 
 
 @pytest.fixture(scope="module")
@@ -184,6 +91,66 @@ def test_ed_madd_pre(harness):
         for i, p in enumerate(seq):
             total = bw.add(total, p)
             assert ext_point(out[128 * i:128 * i + 128]) == total, (seq, i)   # (Z != 0 throughout: P + (-P) is (0 : c : c : 0))
+
+
+# --- the tree through its slots -------------------------------------------------------------------------------------------------------
+TREE_GUARD = bytes.fromhex("dec0dec0") * 64      # the harness's sentinel words in front of and behind the stand-in for LDS
+
+
+def _tree(harness, slots, lanes, first, groups):
+    """groups: per group a list of `lanes` entries, None (the in-memory neutral, all zero) or (scalar, z): [scalar]G scaled by z
+    -> lane 0 of every group after the tree (128 bytes each)"""
+    data = struct.pack("<4I", slots, len(groups), lanes, first)
+    for grp in groups:
+        assert len(grp) == lanes
+        for ent in grp:
+            if ent is None:
+                data += bytes(128)
+            else:
+                x, y = bw.msm_fast([ent[0]], [bw.G])
+                z = ent[1]
+                data += b"".join(bw.fp_bytes(v) for v in (x * z % bw.P, y * z % bw.P, z, x * y * z % bw.P))
+    out = harness("tree", data)
+    n = len(groups)
+    assert len(out) == 128 * n + 512
+    assert out[128 * n:128 * n + 256] == TREE_GUARD and out[128 * n + 256:] == TREE_GUARD     # nothing written outside the slots
+    return [out[128 * g:128 * g + 128] for g in range(n)]
+
+
+def _tree_groups(rng, n_groups, lanes, offset=0):
+    """lane l of group g holds [1000 g + l + 1 + offset]G with a random Z; a few lanes (lane 0 of group 0 among them) the neutral"""
+    return [[None if (7 * l + g) % 13 == 0 else (1000 * g + l + 1 + offset, rng.randrange(1, bw.P)) for l in range(lanes)]
+            for g in range(n_groups)]
+
+
+def _tree_expect(grp, first):
+    """the sum of the lanes the tree reaches from level `first`: those below 2 * first (lane 0 alone when the loop does not run)"""
+    return bw.msm_fast([sum(ent[0] for ent in grp[:max(1, 2 * first)] if ent is not None) % bw.R], [bw.G])
+
+
+def _tree_point(b):
+    return bw.O if b[64:96] == bytes(32) else ext_point(b)
+
+
+@pytest.mark.parametrize("slots,lanes,first,n_groups", [(128, 256, 0, 1), (128, 256, 1, 1), (128, 256, 4, 1), (128, 256, 128, 1), (32, 64, 32, 4)])
+def test_tree_through_its_slots(harness, slots, lanes, first, n_groups):
+    """vk_tree_put / vk_tree_take as k_vk_commit (128 slots, first level live / 2 for n = 1, 2, 8, 256) and k_vk_update (32 slots per
+    wave, four waves) run them.  Every lane holds a point, also those the tree must not reach."""
+    groups = _tree_groups(random.Random(slots + first), n_groups, lanes)
+    if first == 0:
+        groups[0][0] = (1, 3)                                 # (n = 1: lane 0 keeps what it has, whatever it is)
+    got = _tree(harness, slots, lanes, first, groups)
+    for g, grp in enumerate(groups):
+        assert _tree_point(got[g]) == _tree_expect(grp, first), g
+    # no group's result depends on another group's points: the last group's inputs changed, the others bit for bit as before
+    changed = groups[:-1] + _tree_groups(random.Random(99), n_groups, lanes, offset=500)[-1:]
+    again = _tree(harness, slots, lanes, first, changed)
+    assert again[:-1] == got[:-1]
+    assert _tree_point(again[-1]) == _tree_expect(changed[-1], first)
+    if n_groups > 1:
+        assert again[-1] != got[-1]
+        changed = _tree_groups(random.Random(98), n_groups, lanes, offset=700)[:1] + groups[1:]
+        assert _tree(harness, slots, lanes, first, changed)[1:] == got[1:]
 
 
 def _commit(harness, pts, rows, c, fr=False):

@@ -12,7 +12,9 @@ import numpy as np
 import pytest
 
 from tests import _banderwagon as bw
-from tests._verkle import crafted_triples, expected_finish, fr_from, map_fr
+from tests import _verkle
+from tests._verkle import check_outputs as _check, crafted_triples, expected_finish, fr_from, log_point as _log_point, map_fr
+from tests._verkle import prj_bytes as _prj_bytes, pts_array as _pts
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -23,17 +25,12 @@ VP = ctypes.c_void_p
 
 @pytest.fixture(scope="module")
 def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch
+    return _verkle.torch_with_gpu()
 
 
 @pytest.fixture(scope="module")
 def dev(torch_cuda):
-    from constantine_amd import DeviceMsm
-    d = DeviceMsm(0)
-    yield d
-    d.close()
+    yield from _verkle.device_msm()
 
 
 @pytest.fixture(scope="module")
@@ -54,42 +51,12 @@ def verkle_crs(dev):
 @pytest.fixture(scope="module")
 def synth_crs(dev, torch_cuda):
     """256 synthetic points [s_j]G of known s_j, the table made from the device tensor"""
-    from constantine_amd import VerkleCrs
-    d = torch_cuda.empty((256, 64), dtype=torch_cuda.uint8, device="cuda")
-    dev.gen_points("banderwagon", 4242, 256, d)
-    dev.sync()
-    logs = [bw.synth_log(4242, j) for j in range(256)]
-    crs = VerkleCrs(d, ctx=dev.ctx, on_device=True)
-    yield d, logs, crs
-    crs.close()
-
-
-def _pts(points):
-    return np.frombuffer(b"".join(bw.aff_bytes(p) for p in points), dtype=np.uint8).reshape(-1, 64).copy()
+    yield from _verkle.synth_crs(dev, torch_cuda, 4242)
 
 
 def _rows(rows, fr=False):
     enc = bw.fr_bytes if fr else bw.big_bytes
     return np.frombuffer(b"".join(enc(k) for row in rows for k in row), dtype=np.uint8).reshape(len(rows), len(rows[0]), 32).copy()
-
-
-def _prj_bytes(pt):
-    return bw.fp_bytes(pt[0]) + bw.fp_bytes(pt[1]) + bw.fp_bytes(1)
-
-
-def _ser(pt):
-    x = pt[0] if pt[1] >= (bw.P - 1) // 2 else (-pt[0]) % bw.P
-    return x.to_bytes(32, "big")
-
-
-def _check(out, i, pt):
-    assert bytes(out["prj"][i]) == _prj_bytes(pt), i
-    assert bytes(out["ser"][i]) == _ser(pt), i
-    assert fr_from(bytes(out["fr"][i])) == map_fr(pt), i
-
-
-def _log_point(t):
-    return bw.msm_fast([t % bw.R], [bw.G])
 
 
 # --- 1. golden commitment -------------------------------------------------------------------------------------------------------------

@@ -1,105 +1,29 @@
 """Sparse batched Verkle updates without a GPU: the update bodies of csrc/verkle_bodies.h (lane sum, the store that adds the old
-commitment, the parent's delta) compiled for the CPU and run the way k_vk_update runs them -- the lanes of a row's group one by one,
-the kernel's tree, the finish, the delta -- against the Python-integer oracle, and the wiring of ctt_hip_verkle_update_batch and
-VerkleCrs.update on a box without a device.
+commitment, the parent's delta) compiled for the CPU (tests/verkle_harness.cpp) and run the way k_vk_update runs them -- four rows to a
+workgroup, the lanes of a row's wave one by one, the kernel's tree through the wave's own slots, the finish, the delta -- against the
+Python-integer oracle, and the wiring of ctt_hip_verkle_update_batch and VerkleCrs.update on a box without a device.
 
 Expected values are exact curve points (tests/_banderwagon.py): scalars are taken mod 2r on bases that carry the point of order two,
 mod r on points of the prime subgroup."""
 import ctypes
-import os
 import random
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import _banderwagon as bw
-from tests._verkle import fr_from, layout, map_fr
+from tests._verkle import build_harness, fr_from, layout, map_fr, prj_bytes as _prj, ser_bytes
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "constantine_amd")
 TOP = (1 << 253) - 1
-G_LANES = 64          # the kernel's group: one wavefront per row
-
-HARNESS = r'''
-#include <cstdio>
-#include <cstring>
-#include <vector>
-#include "verkle_bodies.h"
-using namespace ctt;
-using F = Banderwagon::F;
-using Fr = Banderwagon::Fr;
-template <class T> static bool rd(T* p, size_t n) { return n == 0 || fread(p, sizeof(T), n, stdin) == n; }
-static void wr(const void* p, size_t bytes) { fwrite(p, 1, bytes, stdout); }
-// every body is instantiated once (they inline all of the field arithmetic)
-static __attribute__((noinline)) XYZZ<F> lane_sum(const VkUpdateArgs& a, uint32_t k, uint32_t l, uint32_t G) { return vk_update_lane_sum<F, Fr>(a, k, l, G); }
-static __attribute__((noinline)) void finish(const VkFinishArgs& f, uint32_t lanes) {
-  for (uint32_t lane = 0; lane < lanes; lane++) vk_finish_body<F, Fr>(f, lane);
-}
-// in: n, c, fr, m, has_base, G, E, n points, row_ptr[m + 1], idx[E] (bytes), deltas[E][8], base[m][24] if has_base
-// out: prj m x 96, ser m x 32, fr m x 32, dfr m x 32
-int main() {
-  uint32_t n, c, fr, m, has_base, G, E;
-  if (!rd(&n, 1) || !rd(&c, 1) || !rd(&fr, 1) || !rd(&m, 1) || !rd(&has_base, 1) || !rd(&G, 1) || !rd(&E, 1)) return 1;
-  std::vector<uint32_t> pts(n * 16), row_ptr(m + 1), deltas((size_t)E * 8 + 1), base((size_t)m * 24 + 1);
-  std::vector<uint8_t> idx(E + 1);
-  if (!rd(pts.data(), n * 16) || !rd(row_ptr.data(), m + 1) || !rd(idx.data(), E) || !rd(deltas.data(), (size_t)E * 8)) return 1;
-  if (has_base && !rd(base.data(), (size_t)m * 24)) return 1;
-  VkTableArgs t;
-  int W;
-  t.lay = window_layout(Banderwagon::BITS, (int)c, &W);
-  t.n = n; t.W = (uint32_t)W; t.rows = vk_row_off(t.lay, t.W); t.stride = VK_REC_WORDS;
-  std::vector<uint32_t> tab((size_t)n * t.rows * t.stride), pre((size_t)n * t.rows * 8);
-  t.pts = pts.data(); t.tab = tab.data(); t.pre = pre.data();
-  for (uint32_t lane = 0; lane < n * t.W; lane++) vk_table_body<F>(t, lane);
-  std::vector<uint32_t> ext((size_t)m * VK_EXT_WORDS, 0x5A5A5A5Au);
-  VkUpdateArgs a{tab.data(), n, t.W, t.lay, t.rows, t.stride, row_ptr.data(), idx.data(), deltas.data(), (int)fr,
-                 has_base ? base.data() : nullptr, m, ext.data()};
-  for (uint32_t k = 0; k < m; k++) {
-    std::vector<XYZZ<F>> lanes(G);
-    for (uint32_t l = 0; l < G; l++) lanes[l] = lane_sum(a, k, l, G);
-    for (uint32_t s = G >> 1; s >= 1; s >>= 1)      // the kernel's tree: the upper half of the live lanes hands over to the lower half
-      for (uint32_t l = 0; l < s; l++) lanes[l] = ed_add<F>(lanes[l], lanes[l + s]);
-    vk_update_store<F>(a, k, lanes[0]);
-  }
-  for (uint32_t l = 0; l < G; l++)                  // a wave without a row holds neutrals (and reads nothing)
-    if (!lane_sum(a, m, l, G).is_inf() || !lane_sum(a, m + 3, l, G).is_inf()) return 3;
-  std::vector<uint32_t> prj((size_t)m * 24), ser((size_t)m * 8), rfr((size_t)m * 8), bfr((size_t)m * 8), dfr((size_t)m * 8, 0x5A5A5A5Au);
-  const uint32_t K = VK_FINISH_CHUNK, fl = (m + K - 1) / K + 2;
-  VkFinishArgs f{ext.data(), VK_EXT_WORDS, m, K, prj.data(), ser.data(), rfr.data()};
-  finish(f, fl);
-  if (has_base) {
-    VkFinishArgs fb{base.data(), 24u, m, K, nullptr, nullptr, bfr.data()};
-    finish(fb, fl);
-  }
-  VkDeltaArgs d{rfr.data(), has_base ? bfr.data() : nullptr, m, dfr.data()};
-  for (uint32_t lane = 0; lane < m + 2; lane++) vk_delta_body<Fr>(d, lane);
-  wr(prj.data(), prj.size() * 4); wr(ser.data(), ser.size() * 4); wr(rfr.data(), rfr.size() * 4); wr(dfr.data(), dfr.size() * 4);
-  return 0;
-}
-'''
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    d = tmp_path_factory.mktemp("verkle_update")
-    cxx = shutil.which("g++") or shutil.which("c++")
-    (d / "vku.cpp").write_text(HARNESS)
-    subprocess.run([cxx, "-O2", "-std=c++17", "-I", os.path.join(PKG, "csrc"), str(d / "vku.cpp"), "-o", str(d / "vku")], check=True)
-
-    def run(data):
-        return subprocess.run([str(d / "vku")], input=data, check=True, capture_output=True).stdout
-    return run
+    return build_harness(tmp_path_factory.mktemp("verkle_update"))
 
 
-def _prj(pt, z=1):
-    """(X, Y, Z) bytes of the affine point scaled by z"""
-    return bw.fp_bytes(pt[0] * z % bw.P) + bw.fp_bytes(pt[1] * z % bw.P) + bw.fp_bytes(z % bw.P)
-
-
-def _update(harness, pts, rows, c, bases=None, fr=False, G=G_LANES):
+def _update(harness, pts, rows, c, bases=None, fr=False):
     """rows: [[(index, delta), ...], ...]; bases: None or m (X, Y, Z)-byte strings.  -> per row (prj, ser, fr, dfr) bytes"""
     enc = bw.fr_bytes if fr else bw.big_bytes
     m = len(rows)
@@ -107,12 +31,12 @@ def _update(harness, pts, rows, c, bases=None, fr=False, G=G_LANES):
     for row in rows:
         row_ptr.append(row_ptr[-1] + len(row))
     E = row_ptr[-1]
-    data = struct.pack("<7I", len(pts), c, 1 if fr else 0, m, 1 if bases is not None else 0, G, E)
+    data = struct.pack("<6I", len(pts), c, 1 if fr else 0, m, 1 if bases is not None else 0, E)
     data += b"".join(bw.aff_bytes(p) for p in pts) + struct.pack(f"<{m + 1}I", *row_ptr)
     data += bytes(i for row in rows for i, _ in row) + b"".join(enc(d) for row in rows for _, d in row)
     if bases is not None:
         data += b"".join(bases)
-    out = harness(data)
+    out = harness("update", data)
     assert len(out) == 192 * m
     prj, ser, rfr, dfr = out[:96 * m], out[96 * m:128 * m], out[128 * m:160 * m], out[160 * m:]
     return [(prj[96 * i:96 * i + 96], ser[32 * i:32 * i + 32], rfr[32 * i:32 * i + 32], dfr[32 * i:32 * i + 32]) for i in range(m)]
@@ -126,8 +50,7 @@ def _expect(pts, row, base_pt=bw.O, mod=None):
 def _check(got, pt, base_pt=bw.O):
     prj, ser, rfr, dfr = got
     assert bw.fp_from(prj[64:]) == 1 and bw.aff_from(prj[:64]) == pt
-    x = pt[0] if pt[1] >= (bw.P - 1) // 2 else (-pt[0]) % bw.P
-    assert ser == x.to_bytes(32, "big")
+    assert ser == ser_bytes(pt)
     assert fr_from(rfr) == map_fr(pt)
     assert int.from_bytes(dfr, "little") < bw.R and fr_from(dfr) == (map_fr(pt) - map_fr(base_pt)) % bw.R
 

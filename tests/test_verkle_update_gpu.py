@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 from tests import _banderwagon as bw
-from tests._verkle import fr_from, map_fr
+from tests import _verkle
+from tests._verkle import check_outputs, fr_from, log_point as _log_point, map_fr, prj_bytes as _prj_bytes, pts_array as _pts
 
 pytestmark = pytest.mark.gpu
 TOP = (1 << 253) - 1
@@ -24,47 +25,18 @@ SEED = 5151
 
 @pytest.fixture(scope="module")
 def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch
+    return _verkle.torch_with_gpu()
 
 
 @pytest.fixture(scope="module")
 def dev(torch_cuda):
-    from constantine_amd import DeviceMsm
-    d = DeviceMsm(0)
-    yield d
-    d.close()
+    yield from _verkle.device_msm()
 
 
 @pytest.fixture(scope="module")
 def synth_crs(dev, torch_cuda):
     """256 synthetic points [s_j]G of known s_j, the table made from the device tensor"""
-    from constantine_amd import VerkleCrs
-    d = torch_cuda.empty((256, 64), dtype=torch_cuda.uint8, device="cuda")
-    dev.gen_points("banderwagon", SEED, 256, d)
-    dev.sync()
-    logs = [bw.synth_log(SEED, j) for j in range(256)]
-    crs = VerkleCrs(d, ctx=dev.ctx, on_device=True)
-    yield d, logs, crs
-    crs.close()
-
-
-def _pts(points):
-    return np.frombuffer(b"".join(bw.aff_bytes(p) for p in points), dtype=np.uint8).reshape(-1, 64).copy()
-
-
-def _log_point(t):
-    return bw.msm_fast([t % bw.R], [bw.G])
-
-
-def _prj_bytes(pt, z=1):
-    return bw.fp_bytes(pt[0] * z % bw.P) + bw.fp_bytes(pt[1] * z % bw.P) + bw.fp_bytes(z % bw.P)
-
-
-def _ser(pt):
-    x = pt[0] if pt[1] >= (bw.P - 1) // 2 else (-pt[0]) % bw.P
-    return x.to_bytes(32, "big")
+    yield from _verkle.synth_crs(dev, torch_cuda, SEED)
 
 
 def _csr(rows, fr=False):
@@ -81,9 +53,7 @@ def _bases(points, rng):
 
 
 def _check(out, i, pt, base_pt=bw.O):
-    assert bytes(out["prj"][i]) == _prj_bytes(pt), i
-    assert bytes(out["ser"][i]) == _ser(pt), i
-    assert fr_from(bytes(out["fr"][i])) == map_fr(pt), i
+    check_outputs(out, i, pt)
     dfr = bytes(out["dfr"][i])
     assert int.from_bytes(dfr, "little") < bw.R and fr_from(dfr) == (map_fr(pt) - map_fr(base_pt)) % bw.R, i
 
