@@ -1,5 +1,5 @@
 // hip_backend.h -- HIP launch layer shared by the per-curve translation units (curve_*.hip) and the
-// engine (msm_engine.hip): stream, stage events, EC kernel templates, per-curve operation table.
+// engine (msm_engine.hip): stream, stage events, EC kernel templates, per-curve operation table.  Out-of-line half: hip_backend.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -651,7 +651,7 @@ struct HipBackend {
   hipEvent_t ev_done[NSLOT] = {};
   float stage_ms[ST_COUNT];
 
-  void init(int dev);  // msm_engine.hip
+  void init(int dev);  // hip_backend.hip
 
   void* alloc(size_t b) {
     void* p = nullptr;
@@ -673,7 +673,7 @@ struct HipBackend {
   void free_host_quiet(void* p) noexcept {
     if (p && hipHostFree(p) != hipSuccess) (void)hipGetLastError();
   }
-  void shutdown() noexcept;   // msm_engine.hip: streams and events of init()
+  void shutdown() noexcept;   // hip_backend.hip: streams and events of init()
   void memset0(void* p, size_t b) { HIP_CHECK(hipMemsetAsync(p, 0, b, stream)); }
   void d2d_async(void* dst, const void* src, size_t b) {
     HIP_CHECK(hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToDevice, stream));
@@ -800,7 +800,7 @@ struct HipBackend {
     HIP_CHECK(hipGetLastError());
   }
   void sync() { HIP_CHECK(hipStreamSynchronize(stream)); }
-  void launch_digits_sort(const SortArgs& a);  // msm_engine.hip
+  void launch_digits_sort(const SortArgs& a);  // hip_backend.hip
   // into: the bucket set holds earlier sums that the runs continue (a later slice of a host-pointer MSM, accum_body_xyzz)
   template <class F>
   void launch_accum(const AccumArgs<F>& a, uint32_t W, bool into = false) {
@@ -875,52 +875,59 @@ struct HipBackend {
 // ---------------------------------------------------------------------------------------------
 // Per-curve operation table: each curve_*.hip instantiates the templates once and exports one of these
 // ---------------------------------------------------------------------------------------------
+// one MSM as the operation table takes it: the coefficients with either the points or the prepared records of cached bases
+struct MsmCall {
+  const void* coefs;        // n x 32 bytes
+  int coef_is_fr;
+  const void* points;       // affine, C-API layout; unused with `prepared`
+  uint32_t n;
+  const void* prepared;     // device records of cached bases (bases_prepare), or with table_c > 0 a window table over table_n bases
+  int table_c;
+  uint32_t table_n;
+  // host-resident coefs (and points): uploaded in `chunks` slices (0 = automatic) underneath the accumulation, through these
+  // device buffers (MsmEngine::submit_host)
+  bool on_host;
+  void* d_stage_coefs;
+  void* d_stage_points;
+  int chunks;
+};
+
 struct CurveOps {
   int curve_id;
-  size_t aff_bytes;
+  size_t aff_bytes, fe_bytes, fr_bytes;   // an affine point, one coordinate, one scalar
+  // --- the MSM engine
   void* (*engine_create)(HipBackend* bk);
   void (*engine_destroy)(void* eng);
-  // split form: at most MsmEngine::NSLOT (3) MSMs in flight per engine; submit returns the slot, or -1 when all are taken;
-  // finish returns 0, or -1 when the slot is not in flight
-  int (*submit)(void* eng, const MsmOptions* opt, const void* d_coefs, int coef_is_fr, const void* d_points, uint32_t n,
-                int* plan);
+  // split form: at most MsmEngine::NSLOT (3) MSMs in flight per engine; submit returns the slot (and plan[0..5] = c, digit windows, K,
+  // G, S, lanes), -1 when all slots are taken or -2 when out of device memory; finish returns 0, or -1 when the slot is not in flight
+  int (*submit)(void* eng, const MsmOptions* opt, const MsmCall* call, int* plan);
   int (*finish)(void* eng, int slot, void* r_host, int out_kind);
-  // host-resident inputs, uploaded in slices underneath the accumulation (MsmEngine::submit_host); chunks 0 = automatic
-  int (*submit_host)(void* eng, const MsmOptions* opt, const void* h_coefs, int coef_is_fr, const void* h_points, uint32_t n,
-                     void* d_stage_coefs, void* d_stage_points, int chunks, int* plan);
-  // cached bases: device records for `n` points (d_points in the C-API layout, device memory); submit against them
+  // cached bases: device records for `n` points (d_points in the C-API layout, device memory)
   void* (*bases_prepare)(void* eng, const void* d_points, uint32_t n);
-  // (table_c > 0: d_prepared is a window table over table_n bases made by table_prepare)
-  int (*submit_bases)(void* eng, const MsmOptions* opt, const void* d_coefs, int coef_is_fr, const void* d_prepared,
-                      uint32_t n, int table_c, uint32_t table_n, int* plan);
-  void (*gen_points)(HipBackend* bk, uint64_t seed, uint64_t first, uint32_t n, void* d_out);
-  void (*field_op)(HipBackend* bk, int op, const void* d_a, const void* d_b, void* d_r, uint32_t n);
-  // host-only: r_aff = sum of n affine points (combining the per-GPU partial results of a sharded MSM,
-  // the `r ~+= partial` of ec_multi_scalar_mul_parallel.nim:427-429)
-  void (*ec_sum_affine)(const void* pts_aff, size_t n, void* r_host, int out_kind);
-  // r = sum of n affine points resident on the device (sum_reduce_vartime); returns the K used
-  int (*sum_reduce)(void* eng, const MsmOptions* opt, const void* d_points, uint32_t n, void* r_host, int out_kind);
-  // dst[i] = affine(src[i]) for n Jacobian (src_kind 1) or projective (2) points, device memory, K points per lane
-  void (*batch_affine)(HipBackend* bk, int src_kind, void* d_dst, const void* d_src, uint32_t n, uint32_t K);
-  size_t fe_bytes;  // one coordinate
-  // ok[j] = [r]P_j is the neutral element (r = the curve order), n points and n flags in device memory
-  void (*subgroup_check)(HipBackend* bk, const void* d_points, uint32_t n, void* d_ok);
   // window table over n bases (MsmEngine::prepare_table): records of 2^(c*w) * P_j for every digit window; c = 0 chooses
   void* (*table_prepare)(void* eng, const void* d_points, uint32_t n, int c, int* c_out);
+  // r = sum of n affine points resident on the device (sum_reduce_vartime); returns the K used
+  int (*sum_reduce)(void* eng, const MsmOptions* opt, const void* d_points, uint32_t n, void* r_host, int out_kind);
+  // --- device primitives on the backend's stream
+  void (*gen_points)(HipBackend* bk, uint64_t seed, uint64_t first, uint32_t n, void* d_out);
+  void (*field_op)(HipBackend* bk, int op, const void* d_a, const void* d_b, void* d_r, uint32_t n);
+  bool (*ec_probe_has)(int op);   // group-law probe ops (field_op with 32 + op) this curve serves
+  // dst[i] = affine(src[i]) for n Jacobian (src_kind 1) or projective (2) points, device memory, K points per lane
+  void (*batch_affine)(HipBackend* bk, int src_kind, void* d_dst, const void* d_src, uint32_t n, uint32_t K);
+  // ok[j] = [r]P_j is the neutral element (r = the curve order), n points and n flags in device memory
+  void (*subgroup_check)(HipBackend* bk, const void* d_points, uint32_t n, void* d_ok);
   // KZG quotient polynomial over the curve's scalar field (msm_bodies.h FrQuotientArgs): d_poly canonical, d_dom Montgomery,
   // z canonical (host, fr_bytes), d_work >= (n + ceil(n/8)) * fr_bytes; q (device, canonical) and y (host, canonical) out.
   // Returns 0, or -2 when z is one of the n-th roots of unity (the caller's other formula applies).
   int (*fr_quotient)(HipBackend* bk, const void* d_poly, const void* d_dom, const void* z_host, uint32_t n, void* d_work,
                      void* d_q, void* y_host);
-  size_t fr_bytes;
-  // the same check on the host, for a handful of host-resident points (a precompile call, one commitment): a single GPU lane
+  // --- host only
+  // r_aff = sum of n affine points (combining the per-GPU partial results of a sharded MSM,
+  // the `r ~+= partial` of ec_multi_scalar_mul_parallel.nim:427-429)
+  void (*ec_sum_affine)(const void* pts_aff, size_t n, void* r_host, int out_kind);
+  // the subgroup check for a handful of host-resident points (a precompile call, one commitment): a single GPU lane
   // walks the 255 dependent doublings of [r]P in ~6.5 ms whatever n is, a CPU core needs ~0.2 ms per G1 point
   void (*subgroup_check_host)(const void* pts_aff, size_t first, size_t step, size_t n, uint8_t* ok);
-  // cached bases (records, or a window table when table_c > 0) with HOST-resident coefficients: the coefficients go up in slices
-  // underneath the accumulation like the pairs of submit_host (MsmEngine::submit_host with d_prepared)
-  int (*submit_host_bases)(void* eng, const MsmOptions* opt, const void* h_coefs, int coef_is_fr, const void* d_prepared, uint32_t n,
-                           int table_c, uint32_t table_n, void* d_stage_coefs, int chunks, int* plan);
-  bool (*ec_probe_has)(int op);   // group-law probe ops (field_op with 32 + op) this curve serves
 };
 
 template <class C>
@@ -934,59 +941,27 @@ struct CurveImpl {
     return e;
   }
   static void destroy(void* e) { delete (Engine*)e; }
-  static int submit(void* eng, const MsmOptions* opt, const void* d_coefs, int coef_is_fr, const void* d_points, uint32_t n,
-                    int* plan) {
+  // the caller's options for this call; the lanes stay the engine's (create)
+  static Engine& with_options(void* eng, const MsmOptions* opt) {
     Engine& e = *(Engine*)eng;
-    uint32_t lanes = e.opt.lanes;
+    const uint32_t lanes = e.opt.lanes;
     e.opt = *opt;
     e.opt.lanes = lanes;
-    int sl = e.submit((const uint32_t*)d_coefs, coef_is_fr != 0, (const Affine<F>*)d_points, n);
-    if (sl < 0) return sl;
-    const MsmPlan& p = e.last_plan;
-    plan[0] = p.c; plan[1] = p.W; plan[2] = (int)p.K; plan[3] = (int)p.G; plan[4] = (int)p.S; plan[5] = (int)lanes;
-    return sl;
+    return e;
   }
-  static int submit_host(void* eng, const MsmOptions* opt, const void* h_coefs, int coef_is_fr, const void* h_points, uint32_t n,
-                         void* d_stage_coefs, void* d_stage_points, int chunks, int* plan) {
-    Engine& e = *(Engine*)eng;
-    uint32_t lanes = e.opt.lanes;
-    e.opt = *opt;
-    e.opt.lanes = lanes;
-    int sl = e.submit_host(h_coefs, coef_is_fr != 0, h_points, n, d_stage_coefs, d_stage_points, chunks);
+  static int submit(void* eng, const MsmOptions* opt, const MsmCall* c, int* plan) {
+    Engine& e = with_options(eng, opt);
+    const int sl = c->on_host ? e.submit_host(c->coefs, c->coef_is_fr != 0, c->points, c->n, c->d_stage_coefs, c->d_stage_points,
+                                              c->chunks, c->prepared, c->table_c, c->table_n)
+                              : e.submit((const uint32_t*)c->coefs, c->coef_is_fr != 0, (const Affine<F>*)c->points, c->n, c->prepared,
+                                         c->table_c, c->table_n);
     if (sl < 0) return sl;
-    const MsmPlan& p = e.last_plan;
-    plan[0] = p.c; plan[1] = p.W; plan[2] = (int)p.K; plan[3] = (int)p.G; plan[4] = (int)p.S; plan[5] = (int)lanes;
-    plan[7] = (int)e.last_chunks;
-    return sl;
-  }
-  static int submit_host_bases(void* eng, const MsmOptions* opt, const void* h_coefs, int coef_is_fr, const void* d_prepared, uint32_t n,
-                               int table_c, uint32_t table_n, void* d_stage_coefs, int chunks, int* plan) {
-    Engine& e = *(Engine*)eng;
-    uint32_t lanes = e.opt.lanes;
-    e.opt = *opt;
-    e.opt.lanes = lanes;
-    int sl = e.submit_host(h_coefs, coef_is_fr != 0, nullptr, n, d_stage_coefs, nullptr, chunks, d_prepared, table_c, table_n);
-    if (sl < 0) return sl;
-    const MsmPlan& p = e.last_plan;
-    plan[0] = p.c; plan[1] = p.Wd; plan[2] = (int)p.K; plan[3] = (int)p.G; plan[4] = (int)p.S; plan[5] = (int)lanes;
-    plan[7] = (int)e.last_chunks;
+    const MsmPlan& p = e.last_plan;   // (Wd: the digit windows -- W without a window table, where W is the 1 of the merged bucket set)
+    plan[0] = p.c; plan[1] = p.Wd; plan[2] = (int)p.K; plan[3] = (int)p.G; plan[4] = (int)p.S; plan[5] = (int)e.opt.lanes;
     return sl;
   }
   static void* bases_prepare(void* eng, const void* d_points, uint32_t n) {
     return ((Engine*)eng)->prepare_bases((const Affine<F>*)d_points, n);
-  }
-  // table_c > 0: d_prepared is a window table over table_n bases (table_prepare)
-  static int submit_bases(void* eng, const MsmOptions* opt, const void* d_coefs, int coef_is_fr, const void* d_prepared,
-                          uint32_t n, int table_c, uint32_t table_n, int* plan) {
-    Engine& e = *(Engine*)eng;
-    uint32_t lanes = e.opt.lanes;
-    e.opt = *opt;
-    e.opt.lanes = lanes;
-    int sl = e.submit((const uint32_t*)d_coefs, coef_is_fr != 0, nullptr, n, d_prepared, table_c, table_n);
-    if (sl < 0) return sl;
-    const MsmPlan& p = e.last_plan;
-    plan[0] = p.c; plan[1] = p.Wd; plan[2] = (int)p.K; plan[3] = (int)p.G; plan[4] = (int)p.S; plan[5] = (int)lanes;
-    return sl;
   }
   static void* table_prepare(void* eng, const void* d_points, uint32_t n, int c, int* c_out) {
     return ((Engine*)eng)->prepare_table((const Affine<F>*)d_points, n, c, c_out);
@@ -1060,10 +1035,7 @@ struct CurveImpl {
     write_result<HF>(r_host, acc, out_kind);
   }
   static int sum_reduce(void* eng, const MsmOptions* opt, const void* d_points, uint32_t n, void* r_host, int out_kind) {
-    Engine& e = *(Engine*)eng;
-    uint32_t lanes = e.opt.lanes;
-    e.opt = *opt;
-    e.opt.lanes = lanes;
+    Engine& e = with_options(eng, opt);
     auto res = e.sum_reduce((const Affine<F>*)d_points, n);
     write_result<typename Engine::HF>(r_host, res, out_kind);
     return (int)e.last_sum_K;
@@ -1128,7 +1100,29 @@ struct CurveImpl {
     return 0;
   }
   static const CurveOps* ops() {
-    static const CurveOps o = {C::ID, sizeof(Affine<F>), create, destroy, submit, finish, submit_host, bases_prepare, submit_bases, gen_points, field_op, ec_sum_affine, sum_reduce, batch_affine, sizeof(F), subgroup_check, table_prepare, fr_quotient, sizeof(typename C::Fr), subgroup_check_host, submit_host_bases, probe_has};
+    static const CurveOps o = [] {
+      CurveOps t{};
+      t.curve_id = C::ID;
+      t.aff_bytes = sizeof(Affine<F>);
+      t.fe_bytes = sizeof(F);
+      t.fr_bytes = sizeof(typename C::Fr);
+      t.engine_create = create;
+      t.engine_destroy = destroy;
+      t.submit = submit;
+      t.finish = finish;
+      t.bases_prepare = bases_prepare;
+      t.table_prepare = table_prepare;
+      t.sum_reduce = sum_reduce;
+      t.gen_points = gen_points;
+      t.field_op = field_op;
+      t.ec_probe_has = probe_has;
+      t.batch_affine = batch_affine;
+      t.subgroup_check = subgroup_check;
+      t.fr_quotient = fr_quotient;
+      t.ec_sum_affine = ec_sum_affine;
+      t.subgroup_check_host = subgroup_check_host;
+      return t;
+    }();
     return &o;
   }
 };

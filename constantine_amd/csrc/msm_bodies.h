@@ -5,7 +5,7 @@
 // sort-then-segmented-reduce pipeline:
 //
 //   sort     Booth signed window digits of every scalar (bigints.nim:806-859), then (point index, sign) entries
-//            grouped by bucket per window: partition by bucket group + LDS sort per group  [kernels in msm_engine.hip]
+//            grouped by bucket per window: partition by bucket group + LDS sort per group  [kernels in hip_backend.hip]
 //   accum    every lane sums K consecutive sorted entries into XYZZ accumulators
 //            (mixed add = the reference's `accumulate`, ec_multi_scalar_mul.nim:177-184);
 //            runs fully inside a lane's range go straight to the bucket array, runs that
@@ -168,7 +168,7 @@ struct SortArgs {
   uint32_t* entries;        // [W][nent]
   uint32_t* maxcount;       // [4]: [0] largest bucket, [2] the head merge's queue count; zeroed by the sort's first kernel (k_part_count)
   uint32_t cap, big;        // k_group_sort: entries per LDS tile; buckets above `big` bypass the LDS image
-  uint32_t xcd_map = 1;     // partition kernels: neighbouring slices on one XCD (msm_engine.hip part_slice_of_block); 0 = slice b to block b
+  uint32_t xcd_map = 1;     // partition kernels: neighbouring slices on one XCD (hip_backend.hip part_slice_of_block); 0 = slice b to block b
   uint32_t staged = 1;      // pass A sweep 2 through an LDS image of the block's output (k_part_scatter_staged); 0 = one store per record
   // Round 5: the sort clears the EMPTY buckets of the set it sorts for (zero_bytes = bytes of one bucket, [W][B] buckets at
   // zero_base; 0 = leave them alone).  The accumulation and the head merge write every non-empty bucket, so this is all of the

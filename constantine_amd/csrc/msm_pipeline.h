@@ -56,7 +56,7 @@ struct MsmOptions {
   // cost model of the window choice: ns per mixed addition (accumulate) / per full addition (reduction) with the chip busy;
   // the engine fills in its curve's figures (msm_bodies.h curve descriptors), the defaults are BLS12-381 G1's
   double acc_ns = 0.142, red_ns = 0.26;
-  // sort pass A (msm_engine.hip).  sort_xcd: neighbouring slices on one XCD (1, default) or slice b to block b (0).  sort_staged:
+  // sort pass A (hip_backend.hip).  sort_xcd: neighbouring slices on one XCD (1, default) or slice b to block b (0).  sort_staged:
   // records staged through an LDS image of the block's output -- 1 = where it pays (default: from 256 bucket groups per window,
   // i.e. ~2^22 pairs, on; measured, profiles/sort_staged_xcd_r04.txt: the sort of 2^22 / 2^24 BLS12-381 pairs 0.545 -> 0.486 /
   // 2.26 -> 2.06 ms, BN254 2^22 0.526 -> 0.464, but 0.148 -> 0.173 ms at 2^20 and 0.056 -> 0.081 at 2^16: there a block has one or

@@ -1270,3 +1270,55 @@ def test_pipelined_stream_placements(name, dev, torch_cuda):
         set_all({})
     for i in (1, 0, 2):
         assert bytes(dev.msm(name, dss[i], dp, sizes[i], coord="aff")) == expect[i], i
+
+
+def test_last_plan_of_every_submit_form(torch_cuda):
+    """ctt_hip_msm_last_plan after every way an MSM reaches the engine -- device inputs (blocking and submit / finish), cached plain
+    records (device coefficients, host coefficients, the ticket form) and a window table (device and host coefficients): the same
+    MSM gives the oracle's result through each, and the plan reports the window bits asked for and the DIGIT windows of the
+    scalar (Pallas: 255 bits at c = 8), for the table forms too, where the merged bucket set counts as one window inside the engine.
+    Both depend on the curve's width and c only; K, G, S and the lanes are the device's business."""
+    import ctypes
+    from constantine_amd import CachedBases, DeviceMsm
+    from constantine_amd.msm import COEF_BIG, _out_kind, _ptr
+    torch = torch_cuda
+    name, n = "pallas", 3000
+    curve = po.CURVES[name]
+    pts = cref.gen_points(name, 931, n)
+    sc = cref.synth_scalars(932, n, curve.scalar_bits)
+    expect = bytes(cref.msm(name, sc, pts, nthreads=NT)[0])
+    ds, dp = _to_dev(torch, sc), _to_dev(torch, pts)
+    eng = DeviceMsm(0)
+    plain = table = None
+    try:
+        eng.set_option("c", 8)
+        plain = CachedBases(name, pts, ctx=eng.ctx)
+        table = CachedBases(name, pts, ctx=eng.ctx, table=True, window_bits=8)
+        assert plain.window_bits == 0 and table.window_bits == 8
+
+        def with_device_coefs(bases):   # ctt_hip_msm_with_bases, coefs_on_device = 1 (CachedBases.msm takes the ticket form for a tensor)
+            r = np.zeros(2 * bases.info.coord_bytes, dtype=np.uint8)
+            torch.cuda.current_stream().synchronize()
+            rc = eng.L.ctt_hip_msm_with_bases(eng.ctx, bases.handle, COEF_BIG, _out_kind(bases.info, "aff"), _ptr(r),
+                                              ctypes.c_void_p(ds.data_ptr()), n, 1)
+            assert rc == 0
+            return r
+
+        forms = [("device", lambda: eng.msm(name, ds, dp, n, coord="aff")),
+                 ("submit + finish", lambda: eng.finish(eng.submit(name, ds, dp, n), coord="aff")),
+                 ("records, device coefficients", lambda: with_device_coefs(plain)),
+                 ("records, host coefficients", lambda: plain.msm(sc, coord="aff")),
+                 ("records, with_bases_submit", lambda: plain.finish(plain.submit(ds, n), coord="aff")),
+                 ("table, device coefficients", lambda: with_device_coefs(table)),
+                 ("table, host coefficients", lambda: table.msm(sc, coord="aff"))]
+        for label, run in forms:
+            got = bytes(run())
+            plan = eng.last_plan()
+            print(label, plan)
+            assert got == expect, label
+            assert (plan["c"], plan["W"]) == (8, 32), (label, plan)
+    finally:
+        for b in (plain, table):
+            if b:
+                b.close()
+        eng.close()
