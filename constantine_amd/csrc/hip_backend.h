@@ -801,6 +801,9 @@ struct HipBackend {
   }
   void sync() { HIP_CHECK(hipStreamSynchronize(stream)); }
   void launch_digits_sort(const SortArgs& a);  // hip_backend.hip
+  // what launch_digits_sort can run (group count, buckets per group, the LDS of pass B, the packed record); it aborts on anything else,
+  // the sort probe (ctt_hip_sort_probe) refuses it
+  static bool sort_plan_in_range(const SortArgs& a);  // hip_backend.hip
   // into: the bucket set holds earlier sums that the runs continue (a later slice of a host-pointer MSM, accum_body_xyzz)
   template <class F>
   void launch_accum(const AccumArgs<F>& a, uint32_t W, bool into = false) {

@@ -549,10 +549,16 @@ void HipBackend::shutdown() noexcept {
   own_stream = false;
 }
 
+bool HipBackend::sort_plan_in_range(const SortArgs& a) {
+  if (a.NG == 0u || a.NG > 16384u || a.B / a.NG > GS_MAXBG) return false;
+  if (2ull * (a.B / a.NG) + 1ull + (uint64_t)a.cap + (uint64_t)a.big > GS_LDS_WORDS) return false;
+  if (!a.merged && a.jbits + 1u + a.gshift > 32u) return false;
+  return !(a.merged && (a.W != 1 || a.gshift_narrow != a.gshift));
+}
+
 void HipBackend::launch_digits_sort(const SortArgs& a) {
   const uint32_t ncol = a.W * a.NG;
-  if (a.NG > 16384u || a.B / a.NG > GS_MAXBG || 2u * (a.B / a.NG) + 1u + a.cap + a.big > GS_LDS_WORDS ||
-      (!a.merged && a.jbits + 1u + a.gshift > 32u) || (a.merged && (a.W != 1 || a.gshift_narrow != a.gshift))) {
+  if (!sort_plan_in_range(a)) {
     fprintf(stderr, "[ctt_msm_hip] FATAL: sort plan out of range (n = %u, c = %d, groups = %u)\n", a.n, a.c, a.NG);
     abort();
   }

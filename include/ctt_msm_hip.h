@@ -276,6 +276,25 @@ int ctt_hip_gen_points(ctt_hip_msm_ctx* ctx, int curve, uint64_t seed, uint64_t 
  * destinations (two records per element), 17 with one (one record), 18 the register form of a + b, 19 of 2a (four records per
  * element: every lane's copy).  -1 for an op the curve does not have. */
 int ctt_hip_field_op(ctt_hip_msm_ctx* ctx, int curve, int op, const void* d_a, const void* d_b, void* d_r, uint32_t n);
+/* kernel unit tests of the digit sort (Booth digits + sort by bucket: the six kernels of csrc/hip_backend.hip behind
+ * HipBackend::launch_digits_sort) on device arrays, with the sort's sizing given by the caller instead of the engine's plan, so that
+ * small inputs reach every path.  d_scalars: n canonical scalars of 8 words below 2^bits.
+ * in[14]: 0 bits (1 .. 255), 1 c (2 .. 20; the windows are balanced over bits + 1 bits as in an MSM), 2 log2 of the bucket groups per set
+ * (-1: what the engine's plan has for n), 3 scalars per partition block (0: the plan's), 4 cap and 5 big of pass B (0: 20480 / 1024),
+ * 6 staged (0 / 1: the scatter form asked for; more than 1024 groups take the direct form), 7 xcd_map (0 / 1), 8 merged (1: the
+ * window-table form, one bucket set, entries are table rows w * id_stride + j), 9 id_stride (merged: >= n), 10 zero_bytes (bytes of
+ * one bucket of the region whose empty buckets are cleared, a multiple of 16; 0: none), 11 .. 13 what the caller's buffers hold:
+ * words of d_entries, words of d_bstart, bytes of d_buckets.
+ * used[11], written on success: cb, r (the first r windows have cb + 1 bits, the others cb), W (bucket sets), Wd (digit windows), B
+ * (buckets per set), NG, gshift, gshift_narrow, nblk, jbits, nent (entries per set: n, or Wd * n when merged).
+ * Outputs, the contract of the sort (csrc/msm_bodies.h, above SortArgs): d_entries [W][nent], d_bstart [W][B + 1], d_maxcount [4],
+ * d_buckets [W][B] x zero_bytes (NULL without zero_bytes).  The intermediate arrays are the call's own; it returns when the sort is done.
+ * -1 (last error set) and NOTHING launched or written for: n = 0 or above 2^31 - 1, bits, c or a flag out of range, a group count
+ * that is no power of two or above B, merged with id_stride < n or more than 2^31 - 1 table rows,
+ * zero_bytes no multiple of 16, a buffer smaller than the derived shape, a NULL pointer, and every plan the sort's launcher cannot
+ * run (more than 16384 groups or 1024 buckets per group, cap + big beyond the LDS tile, a packed record above 32 bits). */
+int ctt_hip_sort_probe(ctt_hip_msm_ctx* ctx, const void* d_scalars, uint32_t n, const int32_t* in, uint32_t* used, void* d_entries,
+                       void* d_bstart, void* d_maxcount, void* d_buckets);
 /* host-only: r (`out_kind` layout) = sum of n affine points -- combines the per-GPU partial results of a
  * sharded MSM (the `r ~+= partial` of ec_multi_scalar_mul_parallel.nim:427-429). Needs no GPU. */
 int ctt_hip_ec_sum_affine(int curve, int out_kind, void* r, const void* pts_aff, size_t n);

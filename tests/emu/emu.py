@@ -126,6 +126,20 @@ def plan(n, bits, lanes, table_c=0, ntab=0):
     return dict(zip(("c", "W", "Wd", "B", "K", "G", "S", "slice", "NG", "gshift", "nent", "cb", "r", "merge_steps"), (int(x) for x in out)))
 
 
+def digits(bits, c, scalars, w0=0, nw=None):
+    """Packed Booth digits ((val - 1) << 1 | neg, 0xffffffff = none) of windows [w0, w0 + nw) of (n, 8) uint32 scalars through
+    for_each_digit<4>, the form the sort kernels instantiate: (nw, n) uint32, and the layout's window count."""
+    scalars = np.ascontiguousarray(scalars, dtype=np.uint32).reshape(-1, 8)
+    L = lib()
+    L.emu_digits.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
+    if nw is None:
+        nw = -(-(bits + 1) // c) - w0
+    out = np.full((nw, scalars.shape[0]), 0xA5A5A5A5, dtype=np.uint32)
+    W = L.emu_digits(bits, c, _p(scalars), scalars.shape[0], w0, nw, _p(out))
+    assert W >= 0
+    return out, W
+
+
 def table_window_bits(ntab, bits):
     return lib().emu_table_window_bits(ctypes.c_uint32(ntab), bits)
 

@@ -483,6 +483,29 @@ int emu_plan(uint32_t n, int bits, uint32_t lanes, int table_c, uint32_t ntab, u
   out[11] = (uint32_t)p.lay.cb; out[12] = (uint32_t)p.lay.r; out[13] = (uint32_t)p.merge_steps;
   return 0;
 }
+// The packed digits of windows [w0, w0 + nw) of n scalars through the register walker in the form the sort kernels instantiate it
+// (for_each_digit<4>, hip_backend.hip PA_NS / PS_NS): four scalars at a time, the ragged last group padded with zero scalars as
+// load_scalars pads it.  out[(w - w0) * n + j]; -1 when the windows asked for are not the layout's.
+int emu_digits(int bits, int c, const uint32_t* scalars, uint32_t n, uint32_t w0, uint32_t nw, uint32_t* out) {
+  int W;
+  const WinLayout L = window_layout(bits, c, &W);
+  if (w0 + nw > (uint32_t)W) return -1;
+  for (uint32_t jb = 0; jb < n; jb += 4) {
+    uint32_t k[4][8];
+    for (uint32_t s = 0; s < 4; s++)
+      for (int q = 0; q < 8; q++) k[s][q] = jb + s < n ? scalars[8ull * (jb + s) + q] : 0u;
+    uint32_t seen = 0;
+    for_each_digit<4>(k, w0, nw, L, [&](uint32_t w, const uint32_t (&d)[4]) {
+      for (uint32_t s = 0; s < 4; s++) {
+        if (jb + s < n) out[(size_t)(w - w0) * n + jb + s] = d[s];
+        else if (d[s] != DIGIT_NONE) abort();   // a padding scalar has no digits
+      }
+      seen++;
+    });
+    if (seen != nw) return -1;
+  }
+  return W;
+}
 int emu_table_window_bits(uint32_t ntab, int bits) { return choose_table_window_bits(ntab, bits); }
 int emu_msm_table(int curve, int coef_is_fr, int out_kind, void* r, const void* coefs, const void* points, size_t ntab, size_t n,
                   int c, int K, int chunks) {
