@@ -32,7 +32,7 @@ static constexpr uint32_t KEY_NONE = 0xffffffffu;
 // F  = coordinate field in the reference's representation (what the C API hands over and takes back)
 // FD = coordinate field the kernels compute in (carry-free limbs where that is faster, see fpu.h)
 // ACC_NS / RED_NS: ns per mixed addition of the accumulate kernel and per full addition of the reduction passes with the whole
-// chip busy, measured on MI355X (profiles/): what the window-size cost model (msm_pipeline.h choose_window_bits) ranks plans by.
+// chip busy, measured on MI355X (profiles/): what the window-size cost model (msm_plan.h choose_window_bits) ranks plans by.
 // NARROW_PRIO_LOG2N: the narrow reduction passes run at raised wave priority (hip_backend.h k_pyr_quad) for MSMs of up to 2^this pairs, 0 = never;
 // measured per curve (profiles/wave_priority_r06.txt: it helps BLS12-381 G1 and BN254 up to 2^19, does nothing for G2 and costs Pallas 3 % at 2^16).
 // WHOLE_TAIL_LOG2N: from 2^this pairs on the accumulation of a pipelined MSM waits for the WHOLE tail of the previous one instead of its wide passes only

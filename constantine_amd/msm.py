@@ -420,7 +420,7 @@ class CttEngine:
         # the table stays below TABLE_BYTES_AUTO; the library itself falls back to plain records when a table does not fit.
         if table is None:
             # rows of the table the library would build: one per digit window, bits/c + 1 with c ~ log2(n) (choose_table_window_bits,
-            # msm_pipeline.h: 13 rows of 128-byte records at 2^20 bases = 1.74 GB; round 3 estimated 17 rows and dropped the table
+            # msm_plan.h: 13 rows of 128-byte records at 2^20 bases = 1.74 GB; round 3 estimated 17 rows and dropped the table
             # for exactly that size)
             n = max(1, len(bases))
             c_est = min(22, max(8, int(np.ceil(np.log2(n)))))

@@ -8,7 +8,7 @@ val - 1 of the window's bucket set; its entry is  j | neg << 31  (merged, the wi
 is the table row  (w * id_stride + j) | neg << 31)."""
 import numpy as np
 
-DEFAULT_CAP, DEFAULT_BIG = 20480, 1024     # what the probe takes for cap = 0 / big = 0 (msm_pipeline.h make_plan)
+DEFAULT_CAP, DEFAULT_BIG = 20480, 1024     # what the probe takes for cap = 0 / big = 0 (msm_plan.h SORT_CAP, SORT_BIG)
 FILL = 0xA5                                # the byte the tests pre-fill entries, bstart and the bucket region with
 GUARD = 64                                 # guard words behind every output
 

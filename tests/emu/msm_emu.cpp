@@ -473,7 +473,7 @@ int emu_msm_host(int curve, int coef_is_fr, int out_kind, void* r, const void* c
   const EmuOps* o = ops_of(curve);
   return o ? o->msm_host(coef_is_fr, out_kind, r, coefs, points, n, c, chunks) : -1;
 }
-// the plan the engine would make (msm_pipeline.h make_plan / make_table_plan): c, W, Wd, B, K, G, S, slice, NG, gshift, nent, cb, r, merge steps
+// the plan the engine would make (msm_plan.h make_plan / make_table_plan): c, W, Wd, B, K, G, S, slice, NG, gshift, nent, cb, r, merge steps
 int emu_plan(uint32_t n, int bits, uint32_t lanes, int table_c, uint32_t ntab, uint32_t* out) {
   MsmOptions o;
   o.lanes = lanes;

@@ -413,7 +413,7 @@ def test_window_table_falls_back_when_memory_or_window_bits_do_not_fit(monkeypat
 
 
 def test_plan_fits_the_gpu_for_any_size():
-    """The plan's roundings (msm_pipeline.h): the accumulate grid -- W rows of ceil(G/64) one-wave workgroups -- never exceeds
+    """The plan's roundings (msm_plan.h): the accumulate grid -- W rows of ceil(G/64) one-wave workgroups -- never exceeds
     the resident wave slots (one workgroup more means a second round of a single wave: measured +28 % on BN254 2^22 at c = 15),
     the partition blocks are at most 512 (2048 from 2^23 pairs on) + a rounding remainder and all of one size, every entry has a lane; for sizes that are
     and are not powers of two, the three scalar widths (253: Banderwagon), both occupancies, and the window-table form."""

@@ -8,7 +8,7 @@ record widths; every comparison is integer equality (tests/_sortref.py check()).
 
 The constants the cases lean on are the kernels' own (csrc/hip_backend.hip): GS_RPT * 1024 = 20 * 1024 = 20480 records stay in
 registers between the two sweeps of k_group_sort, GS_MAXBG = 1024 buckets per group, GS_LDS_WORDS = 39936 words of LDS at most
-(2 * Bg + 1 + cap + big), at most 16384 groups, and the shipped tile sizes cap = 20480, big = 1024 (msm_pipeline.h make_plan)."""
+(2 * Bg + 1 + cap + big), at most 16384 groups, and the shipped tile sizes cap = 20480, big = 1024 (msm_plan.h SORT_CAP, SORT_BIG)."""
 import ctypes
 import functools
 import random
