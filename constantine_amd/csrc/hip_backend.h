@@ -67,6 +67,54 @@ __global__ void __launch_bounds__(CONVERT_BLOCK) k_convert_points(const Affine<F
   }
 }
 
+// The front kernel of the endomorphism split (msm_bodies.h glv_pair_body has what a pair becomes): per pair the canonical scalar and the point in,
+// record j = s1 P, record n + j = s2 phi(P) and the half scalars j and n + j out.  The records leave as in k_convert_points -- through an LDS image,
+// whole lines by consecutive lanes, 16-byte chunks XOR-swizzled -- one half after the other through the same image.  The half scalars are one
+// 16-byte store per lane and half: consecutive lanes, consecutive addresses.
+template <class F, class FD>
+__global__ void __launch_bounds__(CONVERT_BLOCK) k_glv_front(const uint32_t* scalars, const Affine<F>* in, void* out, uint32_t* half, uint32_t n) {
+  constexpr uint32_t STRIDE = gather_stride<FD>(), CH = STRIDE / 16u;
+  extern __shared__ uint4 cv_lds[];
+  const uint32_t t = threadIdx.x;
+  const uint32_t j0 = blockIdx.x * CONVERT_BLOCK, j = j0 + t;
+  union Rec {
+    uint4 q[CH];
+    struct { Affine<FD> a; } v;
+    uint32_t w[STRIDE / 4u];
+  };
+  Rec r1, r2;
+  if (j < n) {
+#pragma unroll
+    for (uint32_t i = 0; i < CH; i++) r1.q[i] = r2.q[i] = make_uint4(0u, 0u, 0u, 0u);
+    const uint4* kp = reinterpret_cast<const uint4*>(scalars + 8ull * j);
+    const uint4 lo = kp[0], hi = kp[1];
+    const uint32_t k[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    const GlvPair<FD> g = glv_pair_body<F, FD>(k, in[j]);
+    r1.v.a = g.p1;
+    r2.v.a = g.p2;
+    r1.w[gather_flag_offset<FD>() / 4u] = g.inf;
+    r2.w[gather_flag_offset<FD>() / 4u] = g.inf;
+    uint4* hp = reinterpret_cast<uint4*>(half);
+    hp[j] = make_uint4(g.h.k1[0], g.h.k1[1], g.h.k1[2], g.h.k1[3]);
+    hp[(uint64_t)n + j] = make_uint4(g.h.k2[0], g.h.k2[1], g.h.k2[2], g.h.k2[3]);
+  }
+  const uint32_t cnt = (n - j0 < (uint32_t)CONVERT_BLOCK ? n - j0 : (uint32_t)CONVERT_BLOCK) * CH;
+#pragma unroll
+  for (int hf = 0; hf < 2; hf++) {
+    if (hf) __syncthreads();   // the first half has been read out of the image
+    if (j < n) {
+#pragma unroll
+      for (uint32_t i = 0; i < CH; i++) cv_lds[t * CH + (i ^ (t & (CH - 1u)))] = hf ? r2.q[i] : r1.q[i];
+    }
+    __syncthreads();
+    uint4* dst = reinterpret_cast<uint4*>((char*)out + ((uint64_t)(hf ? n : 0u) + j0) * STRIDE);
+    for (uint32_t i = t; i < cnt; i += CONVERT_BLOCK) {
+      const uint32_t rec = i / CH, ch = i & (CH - 1u);
+      dst[i] = cv_lds[rec * CH + (ch ^ (rec & (CH - 1u)))];
+    }
+  }
+}
+
 #ifndef CTT_ACCUM_WAVES
 #define CTT_ACCUM_WAVES 2   // waves per SIMD the accumulate kernel is compiled for (register budget 512/waves)
 #endif
@@ -794,6 +842,13 @@ struct HipBackend {
                        (size_t)CONVERT_BLOCK * gather_stride<FD>(), front(), in, out, n);
     HIP_CHECK(hipGetLastError());
   }
+  static constexpr bool GLV_FRONT = true;   // (MsmEngine::kGlv: this backend has the front kernel of the endomorphism split)
+  template <class F, class FD>
+  void launch_glv_front(const uint32_t* scalars, const Affine<F>* in, void* out, uint32_t* half, uint32_t n) {
+    hipLaunchKernelGGL((k_glv_front<F, FD>), grid1(n, CONVERT_BLOCK), dim3(CONVERT_BLOCK),
+                       (size_t)CONVERT_BLOCK * gather_stride<FD>(), front(), scalars, in, out, half, n);
+    HIP_CHECK(hipGetLastError());
+  }
   template <class F>
   void launch_table_next(const Affine<F>* prev, Affine<F>* next, uint32_t n, int c) {
     hipLaunchKernelGGL(k_table_next<F>, grid1(n, EC_BLOCK), dim3(EC_BLOCK), 0, stream, prev, next, n, c);
@@ -901,8 +956,8 @@ struct CurveOps {
   // --- the MSM engine
   void* (*engine_create)(HipBackend* bk);
   void (*engine_destroy)(void* eng);
-  // split form: at most MsmEngine::NSLOT (3) MSMs in flight per engine; submit returns the slot (and plan[0..5] = c, digit windows, K,
-  // G, S, lanes), -1 when all slots are taken or -2 when out of device memory; finish returns 0, or -1 when the slot is not in flight
+  // split form: at most MsmEngine::NSLOT (3) MSMs in flight per engine; submit returns the slot (and plan[0..7] = c, accumulations per pair, K,
+  // G, S, lanes, bucket sets, endomorphism split), -1 when all slots are taken or -2 when out of device memory; finish returns 0, or -1 when the slot is not in flight
   int (*submit)(void* eng, const MsmOptions* opt, const MsmCall* call, int* plan);
   int (*finish)(void* eng, int slot, void* r_host, int out_kind);
   // cached bases: device records for `n` points (d_points in the C-API layout, device memory)
@@ -959,8 +1014,11 @@ struct CurveImpl {
                               : e.submit((const uint32_t*)c->coefs, c->coef_is_fr != 0, (const Affine<F>*)c->points, c->n, c->prepared,
                                          c->table_c, c->table_n);
     if (sl < 0) return sl;
-    const MsmPlan& p = e.last_plan;   // (Wd: the digit windows -- W without a window table, where W is the 1 of the merged bucket set)
-    plan[0] = p.c; plan[1] = p.Wd; plan[2] = (int)p.K; plan[3] = (int)p.G; plan[4] = (int)p.S; plan[5] = (int)e.opt.lanes;
+    // (Wd: the digit windows -- W without a window table, where W is the 1 of the merged bucket set.  With the endomorphism split a pair has two
+    // half scalars of Wd digits each: plan[1] stays the accumulations per input pair, the bucket sets and the split are reported behind it)
+    const MsmPlan& p = e.last_plan;
+    plan[6] = p.W; plan[7] = (int)p.glv;
+    plan[0] = p.c; plan[1] = p.glv ? 2 * p.Wd : p.Wd; plan[2] = (int)p.K; plan[3] = (int)p.G; plan[4] = (int)p.S; plan[5] = (int)e.opt.lanes;
     return sl;
   }
   static void* bases_prepare(void* eng, const void* d_points, uint32_t n) {

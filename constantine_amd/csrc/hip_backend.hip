@@ -30,9 +30,12 @@ static constexpr uint32_t GS_RPT = 20;       // records per lane k_group_sort ke
 static constexpr uint32_t GS_MAXBG = 1024;  // buckets per group (LDS counters; make_plan keeps B/NG below it)
 static constexpr uint32_t ENTRY_INVALID = 0xffffffffu;  // never a valid entry: n <= 2^31 - 1
 
-__device__ __forceinline__ void load_scalar(const uint32_t* __restrict__ scalars, uint32_t j, uint32_t* k) {
-  const uint4* p = reinterpret_cast<const uint4*>(scalars + 8ull * j);
-  uint4 lo = p[0], hi = p[1];
+// kwords = 8, or 4 (the half scalars of the endomorphism split, SortArgs::kwords: the upper four words read as zero, and the digit walk
+// below finds no window there -- the windows of such a plan cover 128 bits)
+__device__ __forceinline__ void load_scalar(const uint32_t* __restrict__ scalars, uint32_t kwords, uint32_t j, uint32_t* k) {
+  const uint4* p = reinterpret_cast<const uint4*>(scalars + (uint64_t)kwords * j);
+  uint4 lo = p[0], hi = make_uint4(0u, 0u, 0u, 0u);
+  if (kwords == 8u) hi = p[1];
   k[0] = lo.x; k[1] = lo.y; k[2] = lo.z; k[3] = lo.w;
   k[4] = hi.x; k[5] = hi.y; k[6] = hi.z; k[7] = hi.w;
 }
@@ -57,7 +60,7 @@ __device__ __forceinline__ void load_scalars(const SortArgs& a, uint32_t jb, uin
   for (int s = 0; s < NS; s++) {
     const uint32_t j = jb + (uint32_t)s * blockDim.x + threadIdx.x;
     if (j < j1) {
-      load_scalar(a.scalars, j, k[s]);
+      load_scalar(a.scalars, a.kwords, j, k[s]);
     } else {
 #pragma unroll
       for (int q = 0; q < 8; q++) k[s][q] = 0u;   // a zero scalar has no digits: no records
@@ -553,6 +556,7 @@ bool HipBackend::sort_plan_in_range(const SortArgs& a) {
   if (a.NG == 0u || a.NG > 16384u || a.B / a.NG > GS_MAXBG) return false;
   if (2ull * (a.B / a.NG) + 1ull + (uint64_t)a.cap + (uint64_t)a.big > GS_LDS_WORDS) return false;
   if (!a.merged && a.jbits + 1u + a.gshift > 32u) return false;
+  if (a.kwords != 8u && (a.kwords != 4u || a.lay.off(a.Wd - 1u) + a.lay.width(a.Wd - 1u) > 128)) return false;
   return !(a.merged && (a.W != 1 || a.gshift_narrow != a.gshift));
 }
 

@@ -39,17 +39,22 @@ static constexpr uint32_t KEY_NONE = 0xffffffffu;
 // (msm_pipeline.h accumulate_pairs), 0 = never: the accumulate kernels of the 9-limb curves own every register of the chip (4 waves x 128), a narrow pass
 // beside them crawls (2 ms instead of 7 us) and costs the accumulation 19 % -- Pallas / Vesta 2^22 5.58 -> 5.02 ms per MSM, BN254 2^21 3.03 -> 2.76
 // (profiles/whole_tail_wait_r06.txt); BLS12-381 G1 leaves registers free and loses 5-19 % when made to wait.
-struct Bls12381G1 { using F = Fp<BLS12_381_Fp>; using FD = FpU<BLS12_381_Fp_U>; using Fr = Fp<BLS12_381_Fr>; static constexpr int BITS = 255; static constexpr int ID = 0; static constexpr double ACC_NS = 0.142, RED_NS = 0.26; static constexpr int NARROW_PRIO_LOG2N = 19; static constexpr int WHOLE_TAIL_LOG2N = 0; };
-struct Bls12381G2 { using F = Fp2<Fp<BLS12_381_Fp>>; using FD = Fp2<FpU<BLS12_381_Fp_U>>; using Fr = Fp<BLS12_381_Fr>; static constexpr int BITS = 255; static constexpr int ID = 1; static constexpr double ACC_NS = 0.467, RED_NS = 1.1; static constexpr int NARROW_PRIO_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 0; };
-struct Bn254G1 { using F = Fp<BN254_Fp>; using FD = FpU<BN254_Fp_U>; using Fr = Fp<BN254_Fr>; static constexpr int BITS = 254; static constexpr int ID = 2; static constexpr double ACC_NS = 0.0685, RED_NS = 0.12; static constexpr int NARROW_PRIO_LOG2N = 19; static constexpr int WHOLE_TAIL_LOG2N = 21; };
-struct Bn254G2 { using F = Fp2<Fp<BN254_Fp>>; using FD = F; using Fr = Fp<BN254_Fr>; static constexpr int BITS = 254; static constexpr int ID = 3; static constexpr double ACC_NS = 0.5, RED_NS = 1.2; static constexpr int NARROW_PRIO_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 0; };
-struct PallasEc { using F = Fp<Pallas_Fp>; using FD = FpU<Pallas_Fp_U>; using Fr = Fp<Vesta_Fp>; static constexpr int BITS = 255; static constexpr int ID = 4; static constexpr double ACC_NS = 0.056, RED_NS = 0.10; static constexpr int NARROW_PRIO_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 21; };
-struct VestaEc { using F = Fp<Vesta_Fp>; using FD = FpU<Vesta_Fp_U>; using Fr = Fp<Pallas_Fp>; static constexpr int BITS = 255; static constexpr int ID = 5; static constexpr double ACC_NS = 0.056, RED_NS = 0.10; static constexpr int NARROW_PRIO_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 21; };
+// GLV_LOG2N / GLV_MAX_LOG2N: a device-resident MSM without cached bases of 2^GLV_LOG2N .. 2^GLV_MAX_LOG2N pairs runs the endomorphism split
+// (bls12_381_glv_split below: two 127-bit half scalars per pair, half the bucket sets), 0 = never -- every curve but BLS12-381 G1.  Measured
+// (profiles/glv_split_r07.txt, ms per MSM with two in flight, without / with): 2^17 0.586 / 0.563, 2^18 0.930 / 0.866, 2^19 1.62 / 1.51, 2^20 2.754 /
+// 2.710 (A/B of two libraries), 2^21 5.51 / 5.44 -- and 2^15 0.362 / 0.385, 2^16 0.421 / 0.428, 2^22 10.24 / 10.46: what the split saves is half a
+// bucket reduction, a constant; what it costs (twice the records written, a slower sort) grows with the pairs.  The option "glv" overrides both.
+struct Bls12381G1 { using F = Fp<BLS12_381_Fp>; using FD = FpU<BLS12_381_Fp_U>; using Fr = Fp<BLS12_381_Fr>; static constexpr int BITS = 255; static constexpr int ID = 0; static constexpr double ACC_NS = 0.142, RED_NS = 0.26; static constexpr int NARROW_PRIO_LOG2N = 19; static constexpr int GLV_LOG2N = 17, GLV_MAX_LOG2N = 21; static constexpr int WHOLE_TAIL_LOG2N = 0; };
+struct Bls12381G2 { using F = Fp2<Fp<BLS12_381_Fp>>; using FD = Fp2<FpU<BLS12_381_Fp_U>>; using Fr = Fp<BLS12_381_Fr>; static constexpr int BITS = 255; static constexpr int ID = 1; static constexpr double ACC_NS = 0.467, RED_NS = 1.1; static constexpr int NARROW_PRIO_LOG2N = 0; static constexpr int GLV_LOG2N = 0, GLV_MAX_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 0; };
+struct Bn254G1 { using F = Fp<BN254_Fp>; using FD = FpU<BN254_Fp_U>; using Fr = Fp<BN254_Fr>; static constexpr int BITS = 254; static constexpr int ID = 2; static constexpr double ACC_NS = 0.0685, RED_NS = 0.12; static constexpr int NARROW_PRIO_LOG2N = 19; static constexpr int GLV_LOG2N = 0, GLV_MAX_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 21; };
+struct Bn254G2 { using F = Fp2<Fp<BN254_Fp>>; using FD = F; using Fr = Fp<BN254_Fr>; static constexpr int BITS = 254; static constexpr int ID = 3; static constexpr double ACC_NS = 0.5, RED_NS = 1.2; static constexpr int NARROW_PRIO_LOG2N = 0; static constexpr int GLV_LOG2N = 0, GLV_MAX_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 0; };
+struct PallasEc { using F = Fp<Pallas_Fp>; using FD = FpU<Pallas_Fp_U>; using Fr = Fp<Vesta_Fp>; static constexpr int BITS = 255; static constexpr int ID = 4; static constexpr double ACC_NS = 0.056, RED_NS = 0.10; static constexpr int NARROW_PRIO_LOG2N = 0; static constexpr int GLV_LOG2N = 0, GLV_MAX_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 21; };
+struct VestaEc { using F = Fp<Vesta_Fp>; using FD = FpU<Vesta_Fp_U>; using Fr = Fp<Pallas_Fp>; static constexpr int BITS = 255; static constexpr int ID = 5; static constexpr double ACC_NS = 0.056, RED_NS = 0.10; static constexpr int NARROW_PRIO_LOG2N = 0; static constexpr int GLV_LOG2N = 0, GLV_MAX_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 21; };
 // Banderwagon: twisted Edwards (a = -5) over the BLS12-381 scalar field; ec.h selects the extended-coordinate law by the field type.
 // The device field is the saturated Fp (FD = F, as for BN254 G2): no carry-free set for this modulus yet, so there is no record
 // conversion and the mixed addition computes x*y itself (10M).  ACC_NS / RED_NS: ESTIMATES, not tuned -- about twice Pallas's figures
 // (saturated field, 10M against 8M+2S); DESIGN.md section 10 has the measured k_accum.
-struct Banderwagon { using F = Fp<Banderwagon_Fp>; using FD = F; using Fr = Fp<Banderwagon_Fr>; static constexpr int BITS = 253; static constexpr int ID = 6; static constexpr double ACC_NS = 0.12, RED_NS = 0.20; static constexpr int NARROW_PRIO_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 0; };
+struct Banderwagon { using F = Fp<Banderwagon_Fp>; using FD = F; using Fr = Fp<Banderwagon_Fr>; static constexpr int BITS = 253; static constexpr int ID = 6; static constexpr double ACC_NS = 0.12, RED_NS = 0.20; static constexpr int NARROW_PRIO_LOG2N = 0; static constexpr int GLV_LOG2N = 0, GLV_MAX_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 0; };
 
 // ---------------------------------------------------------------------------------------------
 // Booth signed digits
@@ -147,7 +152,7 @@ CTT_HD void for_each_digit(const uint32_t (&k)[NS][8], uint32_t w0, uint32_t nw,
 // group regions that every digit window of a block fills (the runs of a block are Wd times longer than without a table),
 // and its records are 64-bit: low bucket bits << 32 | sign << 31 | table row.
 struct SortArgs {
-  const uint32_t* scalars;  // [n][8] canonical
+  const uint32_t* scalars;  // [n][kwords] canonical
   uint32_t n;
   int c;                    // bits of the widest window: B = 2^(c-1)
   WinLayout lay;            // widths and offsets of the digit windows
@@ -176,6 +181,9 @@ struct SortArgs {
   // the accumulation (8 us + a launch gap of a 2^16-pair MSM's chain).
   void* zero_base = nullptr;
   uint32_t zero_bytes = 0;
+  // 32-bit words per scalar in memory: 8, or 4 for the half scalars of the endomorphism split (n is then twice the caller's pairs and the
+  // windows cover 128 bits; the sort kernels read the upper words as zero)
+  uint32_t kwords = 8;
 };
 
 // Fr Montgomery -> canonical (batchFromField, finite_fields.nim:915-920)
@@ -1117,6 +1125,180 @@ template <class C>
 CTT_HD void subgroup_check_body(const Affine<typename C::F>* pts, uint32_t n, uint8_t* ok, uint32_t j) {
   if (j >= n) return;
   ok[j] = point_in_subgroup<C, typename C::F>(pts[j]) ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Endomorphism split of BLS12-381 G1 (round 7).  phi(X, Y) = (beta X, Y) is multiplication by mu = -x^2 mod r on the subgroup (the
+// same beta and mu as the subgroup check above; r = x^4 - x^2 + 1, so mu^2 + mu + 1 = r).  A scalar k is written
+//     k == s1 k1 + s2 k2 mu (mod r),   k1, k2 < 2^127,   s1, s2 signs,
+// and the MSM over n pairs (k, P) becomes one over the 2n pairs (k1, s1 P), (k2, s2 phi(P)) with 127-bit scalars: the same number of
+// Booth digits per input pair, in HALF as many bucket sets -- half the bucket reduction, half the bucket stores of the accumulation.
+// (phi is linear, so both halves share the bucket sets: nothing is applied to a sum afterwards.)  The signs go into the point
+// records, the digit code only ever sees the magnitudes.
+//
+// The split, for any 8-word k < 2^255:
+//   1. k -= r when k >= r (2^255 < 2r: once), then k -> r - k when k > (r-1)/2, remembering the fold: k <= (r-1)/2 < 2^254.
+//   2. q' = floor(floor(k / 2^126) * M / 2^128) with M = floor(2^254 / x^2), an estimate of Q = k / x^2 from below:
+//      Q - q' < 2^126 / x^2 (the bits of k dropped: 0.372) + 1 (M rounded down, times k / 2^126 < 2^128) + 1 (the floor) < 2.372.
+//   3. rem = k - q' x^2 is in [0, 2.372 x^2) -- 130 bits, computed mod 2^160; at most two corrections rem -= x^2, q' += 1 leave
+//      rem in [0, x^2) and q' = floor(Q).  Then round: rem > x^2 / 2 -> rem = x^2 - rem with the sign flipped, q' += 1.
+//   4. k = rem_signed + q x^2 = k1 + (-q) mu with q = round(Q): k1 = |rem_signed| <= x^2 / 2, k2 = q with s2 = -1;
+//      the fold of step 1 flips both signs.
+// Bounds: x^2 = 0xac45a401'0001a402'00000001'00000000 < 2^127.43, so k1 <= x^2 / 2 < 2^126.43; and
+// q <= round(((r-1)/2) / x^2) = round((x^2 - 1) / 2) = x^2 / 2 (x^2 is even) < 2^126.43 as well.  Both halves are below 2^127: the plan
+// for them is make_plan(2n, 127 bits), whose windows cover 128 bits, and the Booth recoding of a half never carries out of its top
+// window.  tests/test_glv_split.py holds the body against Python integers.
+// ---------------------------------------------------------------------------------------------
+struct Bls12381Glv {   // 32-bit words, least significant first
+  static constexpr int BITS = 127;   // bits of a half scalar
+  static constexpr uint32_t R[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u, 0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
+  static constexpr uint32_t R_HALF[8] = {0x80000000u, 0x7fffffffu, 0x7fff2dffu, 0xa9ded201u, 0x04d0ec02u, 0x199cec04u, 0x94cebea4u, 0x39f6d3a9u};   // (r - 1) / 2
+  static constexpr uint32_t X2[4] = {0x00000000u, 0x00000001u, 0x0001a402u, 0xac45a401u};        // x^2
+  static constexpr uint32_t X2_HALF[4] = {0x80000000u, 0x00000000u, 0x8000d201u, 0x5622d200u};   // x^2 / 2
+  static constexpr uint32_t M[4] = {0xbdb3fb8bu, 0x58fdb948u, 0x7807eab7u, 0x5f1afb3cu};         // floor(2^254 / x^2)
+  // beta (Bls12381Endo::BETA) in the carry-free device field: beta * 2^392 mod p in 14 limbs of 28 bits (fpu.h)
+  static constexpr uint32_t BETA_U[14] = {0xa75929au, 0x681b798u, 0x22a3e9du, 0xabc02bfu, 0x4e5bb45u, 0x55e6e7eu, 0x4814117u, 0x6d04f1bu, 0xae3387du, 0x54acb0cu, 0x0a4c74bu, 0x56138b5u, 0xb64e066u, 0x00076f2u};
+};
+// multi-word helpers of the split (N, NA, NB: compile-time word counts, every loop unrolls)
+// d = a - b over N words; returns the borrow (1 when a < b)
+template <int N>
+CTT_HD uint32_t words_sub(uint32_t* d, const uint32_t* a, const uint32_t* b) {
+  uint32_t br = 0;
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    const uint64_t t = (uint64_t)a[i] - (uint64_t)b[i] - (uint64_t)br;
+    d[i] = (uint32_t)t;
+    br = (uint32_t)(t >> 63);
+  }
+  return br;
+}
+// the low NO words of a (NA words) times b (NB words)
+template <int NA, int NB, int NO>
+CTT_HD void words_mul(uint32_t* out, const uint32_t* a, const uint32_t* b) {
+#pragma unroll
+  for (int i = 0; i < NO; i++) out[i] = 0u;
+#pragma unroll
+  for (int i = 0; i < NA; i++) {
+    uint32_t carry = 0;
+#pragma unroll
+    for (int j = 0; j < NB; j++) {
+      if (i + j < NO) {
+        const uint64_t t = (uint64_t)a[i] * (uint64_t)b[j] + (uint64_t)out[i + j] + (uint64_t)carry;
+        out[i + j] = (uint32_t)t;
+        carry = (uint32_t)(t >> 32);
+      }
+    }
+    if (i + NB < NO) out[i + NB] = carry;
+  }
+}
+template <int N>
+CTT_HD void words_select(uint32_t* d, bool c, const uint32_t* a, const uint32_t* b) {
+#pragma unroll
+  for (int i = 0; i < N; i++) d[i] = c ? a[i] : b[i];
+}
+template <int N>
+CTT_HD void words_inc(uint32_t* a, uint32_t by) {
+  uint32_t c = by;
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    const uint32_t s = a[i] + c;
+    c = s < c ? 1u : 0u;
+    a[i] = s;
+  }
+}
+
+struct GlvHalves {
+  uint32_t k1[4], k2[4];   // magnitudes, below 2^127
+  bool neg1, neg2;         // k == (neg1 ? -k1 : k1) + (neg2 ? -k2 : k2) * mu (mod r)
+};
+CTT_HD GlvHalves bls12_381_glv_split(const uint32_t* kin) {
+  using G = Bls12381Glv;
+  uint32_t k[8], t[8];
+  // 1. below r, then at most (r - 1) / 2
+  const bool below = words_sub<8>(t, kin, G::R) != 0u;
+  words_select<8>(k, below, kin, t);
+  const bool fold = words_sub<8>(t, G::R_HALF, k) != 0u;   // k > (r - 1) / 2
+  words_sub<8>(t, G::R, k);
+  words_select<8>(k, fold, t, k);
+  // 2. the estimate of k / x^2 from below
+  uint32_t khi[4], prod[8], q[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) khi[i] = (k[3 + i] >> 30) | (k[4 + i] << 2);   // bits 126 .. 253 (k < 2^254)
+  words_mul<4, 4, 8>(prod, khi, G::M);
+#pragma unroll
+  for (int i = 0; i < 4; i++) q[i] = prod[4 + i];
+  // 3. the remainder (130 bits at most), two corrections, then the rounding
+  uint32_t qx[5], rem[5], x2w[5], d[5];
+  words_mul<4, 4, 5>(qx, q, G::X2);
+  words_sub<5>(rem, k, qx);
+#pragma unroll
+  for (int i = 0; i < 4; i++) x2w[i] = G::X2[i];
+  x2w[4] = 0u;
+#pragma unroll
+  for (int it = 0; it < 2; it++) {
+    const bool ge = words_sub<5>(d, rem, x2w) == 0u;
+    words_select<5>(rem, ge, d, rem);
+    words_inc<4>(q, ge ? 1u : 0u);
+  }
+  GlvHalves h;
+  const bool up = words_sub<4>(d, G::X2_HALF, rem) != 0u;   // rem > x^2 / 2: the nearest multiple of x^2 is the one above
+  words_sub<4>(d, G::X2, rem);
+  words_select<4>(h.k1, up, d, rem);
+  words_inc<4>(q, up ? 1u : 0u);
+#pragma unroll
+  for (int i = 0; i < 4; i++) h.k2[i] = q[i];
+  // 4. k1 carries the sign of the remainder, k2 = -q; the fold flips both
+  h.neg1 = up != fold;
+  h.neg2 = !fold;
+  return h;
+}
+
+// which curves have a split (the engine asks at compile time), its half-scalar width and what it does to a point
+template <class C> struct GlvOf { static constexpr bool HAS = false; static constexpr int BITS = C::BITS; };
+template <> struct GlvOf<Bls12381G1> { static constexpr bool HAS = true; static constexpr int BITS = Bls12381Glv::BITS; };
+
+// What the front kernel of the split path makes of one pair (k, P): the records of s1 P and s2 phi(P) in the device field and the two
+// half scalars.  x, y come out of from_sat and beta x out of one more product: below 2p, like every record of convert_point_body; a negated
+// y is 2p - y, in (0, 2p) as well.  The neutral (0, 0) stays the raw (0, 0) -- 0 * beta = 0, and its y is never negated -- and is flagged
+// in both records.
+template <class FD>
+struct GlvPair {
+  Affine<FD> p1, p2;
+  uint32_t inf;
+  GlvHalves h;
+};
+template <class F, class FD>
+CTT_HD GlvPair<FD> glv_pair_body(const uint32_t* k, const Affine<F>& p) {
+  GlvPair<FD> r;
+  r.h = bls12_381_glv_split(k);
+  r.inf = p.is_inf() ? 1u : 0u;
+  const FD x = FD::from_sat(p.x), y = FD::from_sat(p.y);
+  FD beta;
+#pragma unroll
+  for (int i = 0; i < FD::NL; i++) beta.l[i] = Bls12381Glv::BETA_U[i];
+  r.p1.x = x;
+  r.p1.y = FD::template cneg<2>(y, r.h.neg1 && !r.inf);
+  r.p2.x = FD::mul(x, beta);
+  r.p2.y = FD::template cneg<2>(y, r.h.neg2 && !r.inf);
+  return r;
+}
+// pair j of n, stored: records j and n + j of `out` (gather_stride apart, flag word behind the coordinates as convert_point_body writes
+// it), half scalars j and n + j of half[2n][4].  The GPU kernel (hip_backend.h k_glv_front) stages its record stores through LDS.
+template <class F, class FD>
+CTT_HD void glv_front_body(const uint32_t* scalars, const Affine<F>* in, void* out, uint32_t* half, uint32_t n, uint32_t j) {
+  if (j >= n) return;
+  const GlvPair<FD> r = glv_pair_body<F, FD>(scalars + 8ull * j, in[j]);
+  char* rec1 = (char*)out + (uint64_t)j * gather_stride<FD>();
+  char* rec2 = (char*)out + ((uint64_t)n + j) * gather_stride<FD>();
+  *(Affine<FD>*)rec1 = r.p1;
+  *(uint32_t*)(rec1 + gather_flag_offset<FD>()) = r.inf;
+  *(Affine<FD>*)rec2 = r.p2;
+  *(uint32_t*)(rec2 + gather_flag_offset<FD>()) = r.inf;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    half[4ull * j + i] = r.h.k1[i];
+    half[4ull * ((uint64_t)n + j) + i] = r.h.k2[i];
+  }
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -29,6 +29,7 @@ static inline void sort_sizing(SortArgs& sa, const MsmPlan& p, const MsmOptions&
   sa.NG = p.NG; sa.gshift = p.gshift; sa.gshift_narrow = p.gshift_narrow; sa.slice = p.slice; sa.nblk = p.S;
   sa.jbits = p.jbits;
   sa.cap = p.cap; sa.big = p.big;
+  sa.kwords = p.glv ? 4u : 8u;
   sa.xcd_map = o.sort_xcd ? 1u : 0u;
   sa.staged = (o.sort_staged >= 2 || (o.sort_staged == 1 && p.NG >= 256u)) ? 1u : 0u;
 }
@@ -83,11 +84,17 @@ static inline void cpu_relax() {
 #endif
 }
 
+template <class BK, class = void> struct HasGlvFront : std::false_type {};
+template <class BK> struct HasGlvFront<BK, std::void_t<decltype(BK::GLV_FRONT)>> : std::true_type {};
+
 template <class C, class BK>
 struct MsmEngine {
   using F = typename C::F;    // reference representation (C API)
   using FD = typename C::FD;  // device representation
   static constexpr bool kConvert = !std::is_same<F, FD>::value;
+  // the endomorphism split exists for this curve (msm_bodies.h GlvOf) and the backend has its front kernel (launch_glv_front; a backend says so
+  // with a member GLV_FRONT -- one without it runs every MSM on the plain path)
+  static constexpr bool kGlv = GlvOf<C>::HAS && kConvert && HasGlvFront<BK>::value;
   BK& bk;
   MsmOptions opt;
   MsmPlan last_plan;
@@ -101,11 +108,11 @@ struct MsmEngine {
   static constexpr int NSLOT = 3;
   // bstartS / maxcountS / bucketsS: one per in-flight slot -- the head merge and the first reduction pass of MSM i read them on the tail
   // stream while the sort of MSM i+1 already writes its own (submit(): early tail)
-  Buf part, counts, bstartS[NSLOT], entries, bucketsS[NSLOT], heads, tails, hkey, tkey, rA[2], rP[2], scal, maxcountS[NSLOT], cpoints, totals, gbase, mqueue;
+  Buf part, counts, bstartS[NSLOT], entries, bucketsS[NSLOT], heads, tails, hkey, tkey, rA[2], rP[2], scal, half, maxcountS[NSLOT], cpoints, totals, gbase, mqueue;
 
   explicit MsmEngine(BK& b) : bk(b) {}
   ~MsmEngine() {
-    Buf* all[] = {&part, &gbase, &counts, &entries, &heads, &tails, &hkey, &tkey, &rA[0], &rA[1], &rP[0], &rP[1], &scal, &cpoints, &totals, &mqueue};
+    Buf* all[] = {&part, &gbase, &counts, &entries, &heads, &tails, &hkey, &tkey, &rA[0], &rA[1], &rP[0], &rP[1], &scal, &half, &cpoints, &totals, &mqueue};
     for (int i = 0; i < NSLOT; i++) {
       bk.free_quiet(bstartS[i].p);
       bk.free_quiet(bucketsS[i].p);
@@ -241,6 +248,7 @@ struct MsmEngine {
     uint32_t* d_hkey;
     uint32_t* d_tkey;
     uint32_t* d_mqueue;   // the queue form of the head merge (plan.merge_lmax > 0) only
+    uint32_t* d_half;     // the endomorphism split (plan.glv) only: the half scalars [n][4] the sort reads
   };
   // The workspace of stage 1 and the head merge for plan p in slot sl: every buffer and its size, once.  `sa` gets the sort's sizing
   // and its arrays, `st` what the accumulation and the merge share; returns the canonical scalars' buffer (coef_is_fr only).
@@ -248,7 +256,8 @@ struct MsmEngine {
     sort_sizing(sa, p, opt);
     const SortBytes sb = sort_bytes(sa);
     const size_t lanes = (size_t)p.W * p.G;
-    uint32_t* d_scal = coef_is_fr ? (uint32_t*)need(scal, (size_t)p.n * 32) : nullptr;
+    uint32_t* d_scal = coef_is_fr ? (uint32_t*)need(scal, (size_t)p.pairs() * 32) : nullptr;
+    st.d_half = p.glv ? (uint32_t*)need(half, (size_t)p.n * 16) : nullptr;
     sa.part = (uint32_t*)need(part, sb.part);
     sa.cntA = (uint32_t*)need(counts, sb.cntA);
     sa.gtot = (uint32_t*)need(totals, sb.gtot);
@@ -287,11 +296,24 @@ struct MsmEngine {
     bk.stage_begin(sl, ST_DIGITS);
     sa.scalars = d_coefs;
     if (coef_is_fr) {
-      bk.template launch_fr_from_mont<typename C::Fr>(d_coefs, d_scal, n);
+      bk.template launch_fr_from_mont<typename C::Fr>(d_coefs, d_scal, p.pairs());
       sa.scalars = d_scal;
     }
     const bool convert_late = points_arrive != nullptr;
-    const void* d_points = accum_points(d_points_in, d_prepared, d_converted, n, !convert_late);
+    const void* d_points = nullptr;
+    bool split = false;
+    if constexpr (kGlv) {
+      if (p.glv) {
+        // The endomorphism split: ONE front kernel in place of the conversion reads the canonical scalar and the point of every pair and writes
+        // the records of s1 P (record j) and s2 phi(P) (record n/2 + j) and the two half scalars; digits and sort then run on 4-word scalars,
+        // and everything downstream on a plan of n entries whose windows cover 128 bits (submit(): device-resident inputs only).
+        bk.template launch_glv_front<F, FD>(sa.scalars, d_points_in, d_converted, st.d_half, p.pairs());
+        sa.scalars = st.d_half;
+        d_points = d_converted;
+        split = true;
+      }
+    }
+    if (!split) d_points = accum_points(d_points_in, d_prepared, d_converted, n, !convert_late);
     bk.stage_end(sl, ST_DIGITS);
 
     // Booth digits + sort by bucket (two passes: partition by bucket group, then sort each group inside LDS)
@@ -322,7 +344,7 @@ struct MsmEngine {
     const uint64_t accum_waves = (uint64_t)W * ((p.G + 63u) / 64u);
     // (partitioned chip, HipBackend::partitioned: the tail stream has compute units of its own -- nothing to wait for, no slots to leave)
     // (Curve::WHOLE_TAIL_LOG2N: large MSMs of the curves whose accumulate kernel owns every register wait for the whole tail whatever the grid leaves free)
-    const bool whole_tail = C::WHOLE_TAIL_LOG2N > 0 && p.n >= (1u << C::WHOLE_TAIL_LOG2N);
+    const bool whole_tail = C::WHOLE_TAIL_LOG2N > 0 && p.pairs() >= (1u << C::WHOLE_TAIL_LOG2N);
     if (!bk.partitioned() && (whole_tail || accum_waves + tail_min_free_waves() > (uint64_t)opt.lanes / 64u)) bk.tail_wait();
     bk.wide_wait();   // (nothing to wait for unless the previous reduction put wide passes on the tail stream)
     bk.stage_begin(sl, ST_ACCUM);
@@ -398,8 +420,8 @@ struct MsmEngine {
     // under wide passes), a quarter of the overlap is what remains.
     static const bool wide_early = env_int("CTT_HIP_MSM_WIDE_EARLY", 1) != 0;
     bool forked = forked_early, marked = forked_early && bk.partitioned();   // (partitioned: submit() marked behind the merge)
-    const bool first_pass_on_tail = opt.pyr0_tail == 1 && p.n <= (1u << 17) && !p.merged;   // (MsmOptions::pyr0_tail: measured, off)
-    bk.narrow_priority(C::NARROW_PRIO_LOG2N > 0 && p.n <= (1u << C::NARROW_PRIO_LOG2N));
+    const bool first_pass_on_tail = opt.pyr0_tail == 1 && p.pairs() <= (1u << 17) && !p.merged;   // (MsmOptions::pyr0_tail: measured, off)
+    bk.narrow_priority(C::NARROW_PRIO_LOG2N > 0 && p.pairs() <= (1u << C::NARROW_PRIO_LOG2N));
     for (int pass = 0; pass <= p.c - 2; pass++) {
       PyrArgs<FD> pa{d_buckets, d_pyr, d_q, d_out, B, p.c, pass, 1u};
       const uint32_t ntasks = pyr_pass_tasks(B, p.c, pass);
@@ -468,6 +490,14 @@ struct MsmEngine {
     opt.acc_ns = C::ACC_NS;
     opt.red_ns = C::RED_NS;
     MsmOptions po = opt;
+    // The endomorphism split (msm_bodies.h bls12_381_glv_split): 2n entries of 127 bits in place of n of 255 -- the same accumulations in half the
+    // bucket sets.  Device-resident points without cached records or a table, at the curve's sizes (GLV_LOG2N .. GLV_MAX_LOG2N) or as the option says.
+    bool glv = false;
+    if constexpr (kGlv) {
+      glv = !d_prepared && table_c <= 0 && n <= (1u << 30) && opt.glv != 2 && (opt.glv == 1 || (C::GLV_LOG2N > 0 && n >= (1u << C::GLV_LOG2N) && n <= (1u << C::GLV_MAX_LOG2N)));
+    }
+    const uint32_t pn = glv ? 2u * n : n;                    // entries per bucket set and bits of a scalar the plan is made for
+    const int pbits = glv ? GlvOf<C>::BITS : C::BITS;
     // A caller that keeps MSMs in flight gets the tail of the previous MSM (reduction passes behind the first, bit Horner, result
     // copy: latency-bound, a few dozen waves at a time) run BESIDE this accumulation when the accumulate grid leaves wave slots free
     // (accumulate_pairs); it pays to leave them free on purpose.  Up to 2^17 pairs: 1/16 of the lanes.  (Round 2 took 5/32 -- BLS12-381
@@ -477,7 +507,7 @@ struct MsmEngine {
     if (bk.partitioned()) {
       // (the tail runs on compute units the accumulate grid never sees: opt.lanes counts the main stream's CUs only)
     } else if (other_busy(sl) && n <= (1u << 17) && opt.K <= 0 && table_c <= 0) {
-      if (po.c <= 0) po.c = choose_window_bits(n, C::BITS, opt.lanes, opt.acc_ns, opt.red_ns);
+      if (po.c <= 0) po.c = choose_window_bits(pn, pbits, opt.lanes, opt.acc_ns, opt.red_ns);
       static const uint32_t free32 = (uint32_t)env_int("CTT_HIP_MSM_SMALL_FREE_32NDS", 2);
       po.lanes = (uint32_t)((uint64_t)opt.lanes * (32u - (free32 < 31u ? free32 : 31u)) / 32u);
     } else if (other_busy(sl) && opt.K <= 0 && table_c <= 0 && opt.lanes >= 64u * 1024u && opt.acc_ns >= 0.1) {
@@ -488,21 +518,23 @@ struct MsmEngine {
       // 2^20 2.92 / 2.98, 2^21 5.54 / 5.59, 2^22 10.60 / 10.47; G2 2^18 2.92 / 3.13, 2^20 9.50 / 9.46 -- it pays while that share of the
       // accumulation is well below the wait (profiles/sweep_free_wave_slots_r03.txt).  Not for the 254/255-bit G1 fields (acc_ns < 0.1):
       // their additions are twice as fast, their tail ends before their sort does, and the free slots only cost (Pallas 2^20 1.455 / 1.433).
-      if (po.c <= 0) po.c = choose_window_bits(n, C::BITS, opt.lanes, opt.acc_ns, opt.red_ns);
+      if (po.c <= 0) po.c = choose_window_bits(pn, pbits, opt.lanes, opt.acc_ns, opt.red_ns);
       int Wc;
-      window_layout(C::BITS, po.c, &Wc);
+      window_layout(pbits, po.c, &Wc);
       // 32 slots at least: a narrow pass is up to 64 waves, and a G2 wave needs a SIMD to itself (16 free slots of its 1024
       // measured no gain, 32 did: 3.13 -> 2.92 ms at 2^18)
       const uint32_t nslots = opt.lanes / 64u, free_slots = nslots / 64u > 32u ? nslots / 64u : 32u;
-      const double cost_ms = (double)Wc * n * opt.acc_ns * 1e-6 * free_slots / nslots, wait_ms = 0.1 * opt.acc_ns / 0.142;
+      const double cost_ms = (double)Wc * pn * opt.acc_ns * 1e-6 * free_slots / nslots, wait_ms = 0.1 * opt.acc_ns / 0.142;
       if (cost_ms <= tail_free_cost_ratio() * wait_ms) po.lanes = opt.lanes - 64u * free_slots;
     }
-    const MsmPlan p = table_c > 0 ? make_table_plan(n, C::BITS, table_c, table_n, po) : make_plan(n, C::BITS, po);
+    MsmPlan planned = table_c > 0 ? make_table_plan(n, C::BITS, table_c, table_n, po) : make_plan(pn, pbits, po);
+    planned.glv = glv ? 1u : 0u;
+    const MsmPlan p = planned;
     slots[sl].plan = p;
     last_plan = p;
     try {
       bk.stage_begin(sl, ST_TOTAL);
-      void* d_converted = (kConvert && !d_prepared) ? need(cpoints, (size_t)n * record_stride()) : nullptr;
+      void* d_converted = (kConvert && !d_prepared) ? need(cpoints, (size_t)pn * record_stride()) : nullptr;
       XYZZ<FD>* d_buckets = (XYZZ<FD>*)need(bucketsS[sl], (size_t)p.W * p.B * sizeof(XYZZ<FD>));
       // Round 5 experiment (option front_side = 1; off by default: front_side_applies has the measurements): conversion and sort of a small MSM
       // submitted while another is in flight on the front stream, beside that MSM's head merge and first reduction pass.

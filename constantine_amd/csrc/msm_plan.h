@@ -2,6 +2,7 @@
 // host-pointer call.  Host arithmetic only (msm_bodies.h for WinLayout and horner_groups); msm_pipeline.h runs a plan over a backend.
 #pragma once
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 
 #include <vector>
@@ -36,6 +37,10 @@ struct MsmPlan {
   int h, ngrp;         // bit Horner: bits per group, groups per window (the device returns W*ngrp partial sums)
   int merge_steps;     // wide head-merge tree steps enqueued without knowing the largest bucket (plan_merge_steps)
   uint32_t merge_lmax; // > 0: the queue form of the head merge (msm_bodies.h merge_tail_queue_body) for chains of at most this many heads; 0: the tree
+  // 1 = the endomorphism split (msm_bodies.h bls12_381_glv_split): n is TWICE the caller's pairs -- entry j the first half of pair j, entry n/2 + j
+  // its second -- and the windows are those of a 127-bit scalar (MsmEngine::submit decides; every plan builder leaves 0)
+  uint32_t glv = 0;
+  uint32_t pairs() const { return glv ? n / 2u : n; }   // the caller's pairs
 };
 
 struct MsmOptions {
@@ -67,6 +72,9 @@ struct MsmOptions {
   // BLS12-381 G1 2^16 0.466-0.473 / 0.480, 2^17 0.654-0.657 / 0.676-0.680, BN254 2^16 0.345 / 0.350 -- the fork's event pair costs what the
   // 25 us of overlap give (gpurun_out/r5i)
   int pyr0_tail = 0;
+  // the endomorphism split of a device-resident MSM (curves that have one: msm_bodies.h GlvOf): 0 = at the curve's sizes (GLV_LOG2N .. GLV_MAX_LOG2N),
+  // 1 = at every size, 2 = never.  Option "glv", $CTT_HIP_MSM_GLV.
+  int glv = 0;
 };
 
 // The sort's shipped constants: the floor of a partition slice, pass B's LDS tile (cap) and the bucket size above which its LDS image is
@@ -225,6 +233,12 @@ static inline void plan_finish(MsmPlan& p, const MsmOptions& o, uint32_t min_sli
   if (NG > p.B) NG = p.B;
   while (NG < p.B && p.jbits + 1 + group_shift(p.B, NG) > 32) NG <<= 1;   // (never with jbits = 0: the 64-bit records of the window table)
   plan_set_groups(p, NG);
+  // the packed record (low bucket bits | sign | index) of the sort: 32 bits for every plan that comes through here -- make_plan caps c for it and
+  // the loop above narrows the groups down to single buckets if it must; the split's doubled entry count costs one index bit like any other n
+  if (!p.merged && p.jbits + 1u + p.gshift > 32u) {
+    fprintf(stderr, "[ctt_msm] FATAL: sort record of %u + 1 + %u bits (n = %u, c = %d)\n", p.jbits, p.gshift, p.n, p.c);
+    abort();
+  }
   uint32_t K = o.K > 0 ? (uint32_t)o.K : plan_entries_per_lane(p.nent, p.W, o.lanes);
   if (K < 4) K = 4;
   p.K = K;

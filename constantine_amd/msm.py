@@ -127,7 +127,8 @@ class DeviceMsm:
     def set_option(self, key, value):
         """ctt_hip_msm_set_option: "c", "K", "S", "chunks", "horner_bits", "host_window_sums", "sort_staged", "sort_xcd", "timings", "timings_every",
         and the forms of the head merge and the stream placements of a pipelined MSM: "merge_chain", "merge_lmax", "merge_queue_quad",
-        "early_tail" (default 1), "front_side", "pyr0_tail" (include/ctt_msm_hip.h); 0 = automatic / off.  KeyError for an unknown key."""
+        "early_tail" (default 1), "front_side", "pyr0_tail", and "glv" -- the endomorphism split of BLS12-381 G1: 0 at the curve's measured
+        sizes, 1 always, 2 never -- (include/ctt_msm_hip.h); 0 = automatic / off.  KeyError for an unknown key."""
         if self.L.ctt_hip_msm_set_option(self.ctx, key.encode(), int(value)) != 0:
             raise KeyError(key)
 
@@ -252,9 +253,11 @@ class DeviceMsm:
         return dict(zip(("digits", "sort", "accumulate", "merge", "reduce", "total"), (float(x) for x in ms)))
 
     def last_plan(self):
-        p = np.zeros(6, dtype=np.int32)
-        self.L.ctt_hip_msm_last_plan(self.ctx, _ptr(p), 6)
-        return dict(zip(("c", "W", "K", "G", "S", "lanes"), (int(x) for x in p)))
+        """c, W = accumulations per input pair (the digit windows of the scalar; twice the bucket sets when the endomorphism split
+        ran), K, G, S, lanes, bucket_sets and glv (1 = the split ran)."""
+        p = np.zeros(8, dtype=np.int32)
+        self.L.ctt_hip_msm_last_plan(self.ctx, _ptr(p), 8)
+        return dict(zip(("c", "W", "K", "G", "S", "lanes", "bucket_sets", "glv"), (int(x) for x in p)))
 
 
 def set_devices(devices):

@@ -192,7 +192,8 @@ void ctt_hip_msm_ctx_destroy(ctt_hip_msm_ctx* ctx);
  * window); "merge_queue_quad" 2 = the queue kernel with one lane per chain instead of four; "early_tail" merge and every reduction
  * pass of a pipelined MSM on the tail stream (0 never, 1 automatic -- the default --, 2 whenever pipelining); "front_side"
  * conversion and sort of a pipelined MSM on the front stream (1 whenever pipelining, 2 never); "pyr0_tail" 1 = the first reduction
- * pass of a small MSM on the tail stream.  A context also reads $CTT_HIP_MSM_MERGE_CHAIN, $CTT_HIP_MSM_MERGE_LMAX and
+ * pass of a small MSM on the tail stream; "glv" the endomorphism split of a device-resident BLS12-381 G1 MSM (0 at the curve's
+ * measured sizes, 1 at every size, 2 never; also $CTT_HIP_MSM_GLV).  A context also reads $CTT_HIP_MSM_MERGE_CHAIN, $CTT_HIP_MSM_MERGE_LMAX and
  * $CTT_HIP_MSM_QUAD (reduction passes of at most this many additions run with four lanes per addition) when it is created.
  * A context created with $CTT_HIP_CU_TAIL = r > 0 partitions the chip: its tail stream runs on r compute units of every XCD
  * (hipExtStreamCreateWithCUMask), its main stream on the others -- an experiment of round 6, measured slower than sharing the chip
@@ -256,7 +257,8 @@ int ctt_hip_msm_bases_window_bits(const ctt_hip_msm_bases* bases);
 /* HIP-event stage times (ms) of the last finished MSM: digits, sort, accumulate, merge, reduce, total.  Opt-in: set the
  * option "timings" to 1 first (the events are host time per MSM; without it the call returns zeros). */
 int ctt_hip_msm_last_timings(ctt_hip_msm_ctx* ctx, float* ms, int cap);
-/* plan of the last call: c, W, K, G, S, resident lanes */
+/* plan of the last call: c, W, K, G, S, resident lanes, bucket sets, split.  W is the accumulations per input pair: the digit windows of
+ * the scalar, or -- when the endomorphism split ran (split = 1: BLS12-381 G1, two half scalars per pair) -- twice the bucket sets. */
 int ctt_hip_msm_last_plan(ctt_hip_msm_ctx* ctx, int* out, int cap);
 /* d_out[i] = [s_i]G, deterministic synthetic subgroup points (bench / test inputs) */
 int ctt_hip_gen_points(ctt_hip_msm_ctx* ctx, int curve, uint64_t seed, uint64_t first, uint32_t n, void* d_out);
