@@ -29,7 +29,7 @@ def exported_symbols():
     syms += ["ctt_hip_sum_reduce", "ctt_hip_batch_affine", "ctt_hip_msm_abi_version", "ctt_hip_msm_ctx_create", "ctt_hip_msm_ctx_destroy", "ctt_hip_msm_set_option",
              "ctt_hip_msm_device", "ctt_hip_msm_device_submit", "ctt_hip_msm_device_finish", "ctt_hip_msm_sync", "ctt_hip_msm_bases_create", "ctt_hip_msm_bases_destroy",
              "ctt_hip_msm_with_bases", "ctt_hip_msm_with_bases_submit", "ctt_hip_msm_bases_create_table", "ctt_hip_msm_bases_window_bits", "ctt_hip_msm_last_timings", "ctt_hip_msm_last_plan", "ctt_hip_gen_points",
-             "ctt_hip_field_op", "ctt_hip_sort_probe", "ctt_hip_ec_sum_affine", "ctt_hip_msm_stream", "ctt_hip_msm_wait_stream",
+             "ctt_hip_field_op", "ctt_hip_sort_probe", "ctt_hip_sort_probe_words", "ctt_hip_glv_front_probe", "ctt_hip_ec_sum_affine", "ctt_hip_msm_stream", "ctt_hip_msm_wait_stream",
              "ctt_hip_msm_set_devices", "ctt_hip_msm_set_shard_min", "ctt_hip_subgroup_check", "ctt_hip_fr_quotient",
              "ctt_hip_msm_host", "ctt_hip_msm_available", "ctt_hip_last_error", "ctt_hip_last_error_message", "ctt_hip_clear_last_error",
              # part 3: the MSM's callers under the reference's names + their host-only pieces
@@ -217,6 +217,12 @@ def lib():
     if "ctt_hip_sort_probe" not in missing:
         L.ctt_hip_sort_probe.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp, vp]
         L.ctt_hip_sort_probe.restype = i32
+    if "ctt_hip_sort_probe_words" not in missing:
+        L.ctt_hip_sort_probe_words.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]
+        L.ctt_hip_sort_probe_words.restype = i32
+    if "ctt_hip_glv_front_probe" not in missing:
+        L.ctt_hip_glv_front_probe.argtypes = [vp, i32, vp, vp, u32, vp, vp]
+        L.ctt_hip_glv_front_probe.restype = i32
     L.ctt_hip_ec_sum_affine.argtypes = [i32, i32, vp, vp, sz]
     L.ctt_hip_msm_stream.argtypes = [vp]
     L.ctt_hip_msm_stream.restype = vp

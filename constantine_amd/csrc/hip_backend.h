@@ -970,6 +970,9 @@ struct CurveOps {
   void (*gen_points)(HipBackend* bk, uint64_t seed, uint64_t first, uint32_t n, void* d_out);
   void (*field_op)(HipBackend* bk, int op, const void* d_a, const void* d_b, void* d_r, uint32_t n);
   bool (*ec_probe_has)(int op);   // group-law probe ops (field_op with 32 + op) this curve serves
+  // the front kernel of the endomorphism split alone (launch_glv_front on the caller's arrays, then a wait for it): 0, or -1 and nothing
+  // launched for a curve without a split (msm_bodies.h GlvOf)
+  int (*glv_front)(HipBackend* bk, const void* d_scalars, const void* d_points, uint32_t n, void* d_records, void* d_half);
   // dst[i] = affine(src[i]) for n Jacobian (src_kind 1) or projective (2) points, device memory, K points per lane
   void (*batch_affine)(HipBackend* bk, int src_kind, void* d_dst, const void* d_src, uint32_t n, uint32_t K);
   // ok[j] = [r]P_j is the neutral element (r = the curve order), n points and n flags in device memory
@@ -1088,6 +1091,16 @@ struct CurveImpl {
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(bk->stream));
   }
+  static int glv_front(HipBackend* bk, const void* d_scalars, const void* d_points, uint32_t n, void* d_records, void* d_half) {
+    if constexpr (GlvOf<C>::HAS) {
+      const hipStream_t s = bk->front();
+      bk->template launch_glv_front<F, FD>((const uint32_t*)d_scalars, (const Affine<F>*)d_points, d_records, (uint32_t*)d_half, n);
+      HIP_CHECK(hipStreamSynchronize(s));
+      return 0;
+    } else {
+      return -1;
+    }
+  }
   static void ec_sum_affine(const void* pts_aff, size_t n, void* r_host, int out_kind) {
     using HF = typename Engine::HF;
     const Affine<HF>* p = (const Affine<HF>*)pts_aff;
@@ -1177,6 +1190,7 @@ struct CurveImpl {
       t.gen_points = gen_points;
       t.field_op = field_op;
       t.ec_probe_has = probe_has;
+      t.glv_front = glv_front;
       t.batch_affine = batch_affine;
       t.subgroup_check = subgroup_check;
       t.fr_quotient = fr_quotient;

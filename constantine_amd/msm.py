@@ -209,9 +209,10 @@ class DeviceMsm:
     SORT_PROBE_IN = ("bits", "c", "log2_ng", "slice", "cap", "big", "staged", "xcd_map", "merged", "id_stride", "zero_bytes")
     SORT_PROBE_USED = ("cb", "r", "W", "Wd", "B", "NG", "gshift", "gshift_narrow", "nblk", "jbits", "nent")
 
-    def sort_probe(self, d_scalars, n, d_entries, d_bstart, d_maxcount, d_buckets=None, log2_ng=-1, **sizing):
-        """ctt_hip_sort_probe: the digit sort alone on n device scalars, sized by `sizing` (the names of SORT_PROBE_IN; what is left out is
-        0 = the engine's default).  The outputs are uint32 / uint8 device tensors whose sizes go along as the capacities the call checks.
+    def sort_probe(self, d_scalars, n, d_entries, d_bstart, d_maxcount, d_buckets=None, log2_ng=-1, kwords=8, **sizing):
+        """ctt_hip_sort_probe_words: the digit sort alone on n device scalars of `kwords` words each (8, or 4: the half scalars of the
+        endomorphism split), sized by `sizing` (the names of SORT_PROBE_IN; what is left out is 0 = the engine's default).  The outputs are
+        uint32 / uint8 device tensors whose sizes go along as the capacities the call checks.
         Returns the derived shape (SORT_PROBE_USED) as a dict, or None when the call was refused (nothing launched, nothing written)."""
         unknown = set(sizing) - set(self.SORT_PROBE_IN)
         if unknown:
@@ -221,9 +222,16 @@ class DeviceMsm:
         args = np.array([int(sizing.get(k, 0)) for k in self.SORT_PROBE_IN] + [cap[0] // 4, cap[1] // 4, cap[2]], dtype=np.int32)
         used = np.zeros(len(self.SORT_PROBE_USED), dtype=np.uint32)
         self._order(d_scalars, d_entries, d_bstart, d_maxcount, d_buckets)
-        rc = self.L.ctt_hip_sort_probe(self.ctx, self._dptr(d_scalars), n, _ptr(args), _ptr(used), self._dptr(d_entries), self._dptr(d_bstart),
-                                       self._dptr(d_maxcount), self._dptr(d_buckets) if d_buckets is not None else None)
+        rc = self.L.ctt_hip_sort_probe_words(self.ctx, self._dptr(d_scalars), kwords, n, _ptr(args), _ptr(used), self._dptr(d_entries),
+                                             self._dptr(d_bstart), self._dptr(d_maxcount), self._dptr(d_buckets) if d_buckets is not None else None)
         return dict(zip(self.SORT_PROBE_USED, (int(x) for x in used))) if rc == 0 else None
+
+    def glv_front_probe(self, curve, d_scalars, d_points, n, d_records, d_half):
+        """ctt_hip_glv_front_probe: the front kernel of the endomorphism split alone -- n canonical scalars [n][8] and n affine points in,
+        the records [2n] and the half scalars [2n][4] out (include/ctt_msm_hip.h).  False when the call was refused (nothing launched)."""
+        self._order(d_scalars, d_points, d_records, d_half)
+        dp = lambda t: self._dptr(t) if t is not None else None
+        return self.L.ctt_hip_glv_front_probe(self.ctx, CURVES[curve].cid, dp(d_scalars), dp(d_points), n, dp(d_records), dp(d_half)) == 0
 
     def sum_reduce(self, curve, d_points, n, coord="aff"):
         """r = sum of n affine points resident in HBM (sum_reduce_vartime)."""

@@ -294,9 +294,25 @@ int ctt_hip_field_op(ctt_hip_msm_ctx* ctx, int curve, int op, const void* d_a, c
  * -1 (last error set) and NOTHING launched or written for: n = 0 or above 2^31 - 1, bits, c or a flag out of range, a group count
  * that is no power of two or above B, merged with id_stride < n or more than 2^31 - 1 table rows,
  * zero_bytes no multiple of 16, a buffer smaller than the derived shape, a NULL pointer, and every plan the sort's launcher cannot
- * run (more than 16384 groups or 1024 buckets per group, cap + big beyond the LDS tile, a packed record above 32 bits). */
+ * run (more than 16384 groups or 1024 buckets per group, cap + big beyond the LDS tile, a packed record above 32 bits).
+ * ctt_hip_sort_probe_words is the same call on scalars of `kwords` words each, d_scalars [n][kwords]: 8 (what ctt_hip_sort_probe passes), or
+ * 4 -- the half scalars of the endomorphism split, which the sort reads with the upper four words taken as zero; their windows must end
+ * at bit 128 or below (bits <= 127).  It refuses, as above, every other kwords and 4 words under windows that end above bit 128. */
 int ctt_hip_sort_probe(ctt_hip_msm_ctx* ctx, const void* d_scalars, uint32_t n, const int32_t* in, uint32_t* used, void* d_entries,
                        void* d_bstart, void* d_maxcount, void* d_buckets);
+int ctt_hip_sort_probe_words(ctt_hip_msm_ctx* ctx, const void* d_scalars, uint32_t kwords, uint32_t n, const int32_t* in, uint32_t* used,
+                             void* d_entries, void* d_bstart, void* d_maxcount, void* d_buckets);
+/* kernel unit tests of the endomorphism split (BLS12-381 G1): the front kernel of the split path alone on device arrays -- what an MSM
+ * of 2^17 .. 2^21 device-resident pairs runs in place of the point conversion.  d_scalars: n canonical scalars of 8 words below 2^255;
+ * d_points: n affine points in the C-API layout.  Outputs, as the sort and the accumulation then read them: d_records [2n] records of
+ * 128 bytes -- x, y in the device field (14 limbs of 28 bits each, value * 2^392 mod p up to a multiple of p, below 2p) and a flag word
+ * at byte 112 (1 = the neutral element, whose coordinates stay zero) --, record j = s1 P_j and record n + j = s2 phi(P_j) with
+ * phi(x, y) = (beta x, y) = [mu](x, y), the signs in y; d_half [2n][4] words, half scalar j = k1 and n + j = k2, both at most x^2 / 2
+ * < 2^127, with k == s1 k1 + s2 k2 mu (mod r).  d_scalars, d_records and d_half must be 16-byte aligned (the kernel moves all three in
+ * 16-byte pieces; hipMalloc's alignment is more than enough).  It returns when the kernel is done.
+ * -1 (last error set) and NOTHING launched or written for a curve without a split, n = 0 or above 2^30, and a NULL pointer. */
+int ctt_hip_glv_front_probe(ctt_hip_msm_ctx* ctx, int curve, const void* d_scalars, const void* d_points, uint32_t n, void* d_records,
+                            void* d_half);
 /* host-only: r (`out_kind` layout) = sum of n affine points -- combines the per-GPU partial results of a
  * sharded MSM (the `r ~+= partial` of ec_multi_scalar_mul_parallel.nim:427-429). Needs no GPU. */
 int ctt_hip_ec_sum_affine(int curve, int out_kind, void* r, const void* pts_aff, size_t n);

@@ -70,6 +70,18 @@ int emu_glv_msm_slots(void* r3, const void* coefs_a, const void* points_a, size_
   for (int i = 0; i < 3; i++) write_result<HF>((char*)r3 + (size_t)i * sizeof(Affine<F>), eng.finish(t[i]), OUT_AFF);
   return 0;
 }
+// the front body alone (msm_bodies.h glv_front_body), the CPU twin of ctt_hip_glv_front_probe: n canonical scalars [n][8] and n affine points in,
+// records [2n][gather_stride] and half scalars [2n][4] out.  shape (may be NULL): gather_stride, gather_flag_offset, limbs per coordinate, limb bits
+int emu_glv_front(const uint32_t* scalars, const void* points, uint32_t n, void* records, uint32_t* half, uint32_t* shape) {
+  using C = Bls12381G1;
+  using F = C::F;
+  using FD = C::FD;
+  if (shape) {
+    shape[0] = gather_stride<FD>(); shape[1] = gather_flag_offset<FD>(); shape[2] = (uint32_t)FD::NL; shape[3] = (uint32_t)FD::LB;
+  }
+  for (uint32_t j = 0; j < n; j++) glv_front_body<F, FD>(scalars, (const Affine<F>*)points, records, half, n, j);
+  return 0;
+}
 // the split body (msm_bodies.h bls12_381_glv_split) of n scalars of 8 words: out[j] = k1 (4 words), k2 (4 words), neg1, neg2
 int emu_glv_split(const uint32_t* scalars, uint32_t n, uint32_t* out) {
   for (uint32_t j = 0; j < n; j++) {

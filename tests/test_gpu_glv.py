@@ -4,7 +4,9 @@ The endomorphism split of BLS12-381 G1 on the GPU (run with -m gpu on an MI355X)
 
 The inputs are the synthetic points [s_i]G of known s_i (oracle/cref.py gen_point_scalars), so the expected element is ONE scalar
 multiplication of oracle/pyoracle.py: [sum k_i s_i mod r]G -- no elliptic-curve code shared with what is tested.  The CPU twin of this
-file is tests/test_glv_split.py.
+file is tests/test_glv_split.py; the front kernel alone is held pair by pair in tests/test_glv_front_probe.py and the sort on half
+scalars in tests/test_sort_probe.py.  Here also: the sizes at which the split runs by default, cached bases and window tables under the
+forcing option, and scalars outside the contract on the split path.
 """
 import numpy as np
 import pytest
@@ -131,15 +133,21 @@ def test_three_in_flight_alternating_inputs(cases, eng, torch_cuda):
         assert bytes(eng.finish(t, coord="aff")) == e, j
 
 
+# the sizes at which a device-resident MSM without cached bases takes the split by default: 2^GLV_LOG2N .. 2^GLV_MAX_LOG2N pairs
+# (csrc/msm_bodies.h Bls12381G1::GLV_LOG2N, GLV_MAX_LOG2N)
+GLV_LOG2N, GLV_MAX_LOG2N = 17, 21
+
+
 def test_default_follows_the_curve_sizes(cases, torch_cuda):
     """option "glv" = 0: the split runs at the curve's sizes (msm_bodies.h GLV_LOG2N .. GLV_MAX_LOG2N; 0 = never) and never on the
     other curves; the result is the same either way"""
     from constantine_amd import DeviceMsm
     ds, dp, sc, expect = cases[4096]
+    assert 4096 < 1 << GLV_LOG2N
     d = DeviceMsm(0)
     try:
         assert bytes(d.msm(NAME, ds, dp, 4096, coord="aff")) == expect
-        assert d.last_plan()["glv"] in (0, 1)
+        assert d.last_plan()["glv"] == 0
         d.set_option("glv", 1)
         name = "bn254_snarks_g1"
         n = 300
@@ -150,3 +158,76 @@ def test_default_follows_the_curve_sizes(cases, torch_cuda):
         assert bytes(got) == want and d.last_plan()["glv"] == 0
     finally:
         d.close()
+
+
+BOUNDS_SEED = 9500
+
+
+@pytest.fixture(scope="module")
+def bounds_inputs(torch_cuda, eng):
+    """2^GLV_MAX_LOG2N + 1 synthetic pairs on the device; every size of the test below is a prefix of them"""
+    n = (1 << GLV_MAX_LOG2N) + 1
+    d_pts = torch_cuda.empty((n, CURVE.aff_bytes), dtype=torch_cuda.uint8, device="cuda")
+    eng.gen_points(NAME, BOUNDS_SEED, n, d_pts)
+    sc = cref.synth_scalars(BOUNDS_SEED + 1, n, 255)
+    return torch_cuda.from_numpy(sc).cuda(), d_pts, sc
+
+
+@pytest.mark.parametrize("n, glv", [((1 << GLV_LOG2N) - 1, 0), (1 << GLV_LOG2N, 1), (1 << GLV_MAX_LOG2N, 1), ((1 << GLV_MAX_LOG2N) + 1, 0)])
+def test_default_split_range_is_exactly_the_curve_sizes(n, glv, bounds_inputs):
+    """a fresh context with no option set, one pair below, at both ends of and one pair above GLV_LOG2N .. GLV_MAX_LOG2N: the plan says
+    whether the split ran, and the result is [sum k_i s_i mod r]G either way (the dot product over the known discrete logs runs on 16-bit
+    limbs in numpy: oracle/cref.py msm_by_discrete_logs)"""
+    from constantine_amd import DeviceMsm
+    ds, dp, sc = bounds_inputs
+    expect = CURVE.aff_to_bytes(cref.msm_by_discrete_logs(NAME, BOUNDS_SEED, sc[:n]))
+    d = DeviceMsm(0)
+    try:
+        assert bytes(d.msm(NAME, ds, dp, n, coord="aff")) == expect, d.last_plan()
+        plan = d.last_plan()
+        assert plan["glv"] == glv, plan
+        assert plan["W"] == (2 if glv else 1) * plan["bucket_sets"], plan
+    finally:
+        d.close()
+
+
+@pytest.mark.parametrize("n", [4096, 1 << GLV_LOG2N])
+@pytest.mark.parametrize("table", [False, True], ids=["records", "table"])
+def test_cached_bases_stay_on_the_plain_path(n, table, bounds_inputs, eng):
+    """option "glv" = 1 forces the split for device-resident points only: cached records and a window table have no front stage"""
+    from constantine_amd import CachedBases
+    ds, dp, sc = bounds_inputs
+    expect = CURVE.aff_to_bytes(cref.msm_by_discrete_logs(NAME, BOUNDS_SEED, sc[:n]))
+    bases = CachedBases(NAME, dp[:n], ctx=eng.ctx, on_device=True, table=table)
+    try:
+        assert (bases.window_bits > 0) == table
+        assert bytes(bases.msm(ds[:n], coord="aff")) == expect, eng.last_plan()
+        plan = eng.last_plan()
+        assert plan["glv"] == 0, plan
+        if table:
+            assert plan["bucket_sets"] == 1, plan
+        # and the same pairs without the cache take the split on this context
+        assert bytes(eng.msm(NAME, ds, dp, n, coord="aff")) == expect and eng.last_plan()["glv"] == 1
+    finally:
+        bases.close()
+
+
+def test_scalars_beyond_the_bit_width_on_the_split_path(bounds_inputs, eng, torch_cuda):
+    """Scalars of 2^255 and above are outside the contract of the split as of every MSM (its reduction subtracts r once and its quotient
+    estimate reads bits 126 .. 253): with bits 254 and 255 set the halves are unspecified and may have bit 127 set.  What holds is what
+    tests/test_gpu_parity.py holds for BN254: every call returns, nothing is corrupted, and the next in-contract call on the same
+    context is exact."""
+    ds, dp, sc = bounds_inputs
+    n = 50000
+    bad = np.full((n, 32), 0xFF, dtype=np.uint8)
+    bad[::3] = sc[:n:3]
+    d_bad = torch_cuda.from_numpy(bad).cuda()
+    try:
+        for c in (0, 16, 13):
+            eng.set_option("c", c)
+            eng.msm(NAME, d_bad, dp, n, coord="aff")                      # must return
+            assert eng.last_plan()["glv"] == 1
+    finally:
+        eng.set_option("c", 0)
+    expect = CURVE.aff_to_bytes(cref.msm_by_discrete_logs(NAME, BOUNDS_SEED, sc[:n]))
+    assert bytes(eng.msm(NAME, ds, dp, n, coord="aff")) == expect and eng.last_plan()["glv"] == 1

@@ -6,6 +6,10 @@ run on the host by tests/emu) against the reference, the shape of every crafted 
 probe without a device.  Second half, `gpu`: every case through the probe over both scatter forms, both block-to-slice maps and both
 record widths; every comparison is integer equality (tests/_sortref.py check()).
 
+The same for the 4-word half scalars of the endomorphism split (SortArgs::kwords == 4, load_scalar in csrc/hip_backend.hip), through
+ctt_hip_sort_probe_words: the device gets the low four words [n][4], the reference the same scalars zero-extended to 8 words with
+bits = 127 -- the layouts whose windows end at bit 128 (cases_half below).
+
 The constants the cases lean on are the kernels' own (csrc/hip_backend.hip): GS_RPT * 1024 = 20 * 1024 = 20480 records stay in
 registers between the two sweeps of k_group_sort, GS_MAXBG = 1024 buckets per group, GS_LDS_WORDS = 39936 words of LDS at most
 (2 * Bg + 1 + cap + big), at most 16384 groups, and the shipped tile sizes cap = 20480, big = 1024 (msm_plan.h SORT_CAP, SORT_BIG)."""
@@ -18,6 +22,7 @@ import pytest
 
 from oracle import pyoracle as po
 from tests import _banderwagon as bw
+from tests import _glvref as gr
 from tests import _sortref as sr
 
 GS_REGS, GS_MAXBG, GS_LDS_WORDS, MAX_GROUPS = 20 * 1024, 1024, 39936, 16384
@@ -58,10 +63,15 @@ def _craft(lay, n, windows, seed):
 class Case:
     """One input of the probe: scalars and sizing.  `table`: the case is also run in the window-table form (merged, id_stride = n + 3)."""
 
-    def __init__(self, name, ks, bits, c, log2_ng, slice_=256, cap=0, big=0, table=False, variants=VARIANTS):
+    def __init__(self, name, ks, bits, c, log2_ng, slice_=256, cap=0, big=0, table=False, variants=VARIANTS, kwords=8):
         self.name, self.bits, self.c, self.log2_ng, self.slice, self.cap, self.big = name, bits, c, log2_ng, slice_, cap, big
-        self.n, self.table, self.variants = len(ks), table, variants
-        self.words = sr.to_words(ks)
+        self.n, self.table, self.variants, self.kwords = len(ks), table, variants, kwords
+        self.words = sr.to_words(ks)                       # what the reference reads: 8 words, the upper four zero when kwords == 4
+        assert kwords == 8 or (kwords == 4 and not self.words[:, 4:].any())
+
+    def device_words(self):
+        """what the device gets: [n][kwords]"""
+        return np.ascontiguousarray(self.words[:, :self.kwords])
 
     def sizing(self, merged=0):
         return dict(bits=self.bits, c=self.c, slice=self.slice, cap=self.cap, big=self.big, merged=merged,
@@ -174,7 +184,54 @@ def cases_table():
             Case("table-c13-ng1024", _random_scalars(74, 1499, 255), 255, 13, 10)]
 
 
+# 8. the half scalars of the endomorphism split: 4 words per scalar, bits = 127, windows over 128 bits.  (c, log2 NG):
+#      c = 16   8 windows of 16 bits, B = 2^15, 32 groups: the shipped shape
+#      c = 13   10 windows: 8 of 13 bits and 2 narrow ones of 12 (gshift_narrow = gshift - 1 on the top windows), 8 groups
+#      c = 8    16 windows;   c = 5   26 windows, the first 24 of 5 bits
+#    Scalars: seeded values below 2^127; the real halves of the Python split of seeded scalars (255 bits; below x^2 / 2, whose second
+#    half is zero; a few x^2 and a little, whose second half is tiny: few or no records); 2^127 - 1; the largest top-window digit with a
+#    carry from below (as _narrow_scalars crafts it); zero.  (Plain form only: a table never has half scalars.)
+HALF_BITS = 127
+HALF_LAYOUTS = ((16, 5), (13, 3), (8, 2), (5, 2))
+
+
+def _real_halves(seed, count):
+    rng = random.Random(seed)
+    ks = [rng.getrandbits(255) for _ in range(count)] + [rng.randrange(gr.X2 // 2) for _ in range(count // 2)]
+    ks += [rng.randrange(1, 9) * gr.X2 + rng.randrange(1 << 40) for _ in range(count // 2)]
+    out = []
+    for k in ks:
+        s = gr.split(k)
+        out += [s.k1, s.k2]
+    return out
+
+
+def _half_scalars(c, n, seed):
+    lay = sr.window_layout(HALF_BITS, c)
+    top = lay.W - 1
+    off, cw = lay.off(top), lay.width(top)
+    assert off + cw == 128
+    ks = [(1 << 127) - 1, 0] + [((1 << (cw - 1)) - 1) << off | 1 << (off - 1)] * 3 + [1]
+    ks += _real_halves(seed, (n + 7) // 8)
+    ks = _random_scalars(seed + 1, 1, HALF_BITS) + ks        # (n = 1: a seeded value)
+    ks += _random_scalars(seed + 2, max(0, n - len(ks)), HALF_BITS)
+    assert all(k < (1 << HALF_BITS) for k in ks)
+    return ks[:n]
+
+
+def cases_half():
+    out = []
+    for c, lg in HALF_LAYOUTS:
+        out += [Case(f"half-c{c}-n{n}", _half_scalars(c, n, 800 + 10 * c + n), HALF_BITS, c, lg, kwords=4) for n in (1, 65, 3001)]
+    out.append(Case("half-zero-n3001", [0] * 3001, HALF_BITS, 16, 5, kwords=4))
+    out.append(Case("half-zero-n1", [0], HALF_BITS, 13, 3, kwords=4))
+    s = 2 * 4096 + 256
+    out.append(Case("half-long-slice", _half_scalars(16, 2 * s + 77, 899), HALF_BITS, 16, 5, slice_=s, kwords=4))
+    return out
+
+
 ORDINARY = cases_small() + cases_map() + cases_narrow() + cases_many_groups()
+HALF = cases_half()
 CRAFTED = [case_thresholds(), case_tiles()]
 TABLE_ONLY = cases_table()
 
@@ -189,7 +246,7 @@ def _edge_scalars(bits):
     return ks + _random_scalars(7 * bits, 200, bits)
 
 
-@pytest.mark.parametrize("bits", [253, 254, 255])
+@pytest.mark.parametrize("bits", [127, 253, 254, 255])
 def test_reference_digits_recompose_the_scalar(bits):
     """sum_w +-val_w * 2^off(w) == k for every c, with Python integers; the vectorised digits equal the integer ones; the layout equals
     the engine's wherever its plan takes that c."""
@@ -219,11 +276,12 @@ def test_reference_digits_recompose_the_scalar(bits):
     assert len(seen) >= 3
 
 
-@pytest.mark.parametrize("bits", [253, 254, 255])
+@pytest.mark.parametrize("bits", [127, 253, 254, 255])
 def test_digit_walker_of_the_kernels_at_four_scalars(bits):
     """for_each_digit<4> (what k_part_count and the scatter kernels instantiate) on the host against the reference: every c, whole
     walks and walks over windows [w0, w0 + nw) with w0 > 0 and nw < Wd, a ragged last group of scalars.  c = 16 at 255 bits starts
-    every other window at bit 31 of a word, c = 2 has 128 windows, c = 20 straddles words at every offset."""
+    every other window at bit 31 of a word, c = 2 has 128 windows, c = 20 straddles words at every offset.  bits = 127: the layouts over
+    128 bits of the half scalars, the upper four words zero -- what load_scalar hands the walker for kwords == 4."""
     from tests.emu import emu
     ks = _edge_scalars(bits)
     while len(ks) % 4 != 3:                        # a ragged last group of three
@@ -330,6 +388,44 @@ def test_shape_of_the_tile_case():
     assert all(s["counts"].sum() == 0 for s in exp[6:])
 
 
+def test_shape_of_the_half_cases():
+    """the reference works for the four layouts over 128 bits, and the cases hold what they are named for"""
+    shapes = {16: (8, 16, 0), 13: (10, 12, 8), 8: (16, 8, 0), 5: (26, 4, 24)}            # c: (windows, cb, r)
+    by = {c.name: c for c in HALF}
+    assert len(by) == len(HALF) == 4 * 3 + 3 and all(c.kwords == 4 and c.bits == 127 and not c.table for c in HALF)
+    for c, lg in HALF_LAYOUTS:
+        lay = sr.window_layout(HALF_BITS, c)
+        assert (lay.W, lay.cb, lay.r) == shapes[c] and lay.cmax() == c and lay.off(lay.W - 1) + lay.width(lay.W - 1) == 128
+        for n in (1, 65, 3001):
+            case = by[f"half-c{c}-n{n}"]
+            u, exp = case.used(), case.expected()
+            assert case.n == n and case.device_words().shape == (n, 4) and (u["W"], u["NG"], u["B"]) == (lay.W, 1 << lg, 1 << (c - 1))
+            assert u["gshift_narrow"] == (u["gshift"] - 1 if lay.r else u["gshift"]) and u["B"] >> u["gshift"] == u["NG"]
+            assert len(exp) == lay.W
+            ks = sr.from_words(case.words)
+            for j, k in enumerate(ks[:40]):                                             # the reference's digits recompose the half
+                assert sum((-v if s else v) << lay.off(w) for w, (v, s) in enumerate(sr.booth_digit(k, w, lay) for w in range(lay.W))) == k
+            if n > 1:
+                top = exp[lay.W - 1]["counts"]
+                assert top[(1 << (lay.width(lay.W - 1) - 1)) - 1] >= 3                  # the largest top-window digit, by the carry
+                assert (1 << 127) - 1 in ks and 0 in ks and any(0 < k < 1 << 64 for k in ks)
+                assert any(bool((s["entries"] >> 31).any()) and not bool((s["entries"] >> 31).all()) for s in exp)   # both signs
+            if n == 3001:
+                assert all(_groups(case, w)[0].min() > 0 for w in range(lay.W - 1))     # every group of every window but the top holds records
+                small = sum(1 for k in ks if k < 1 << 48)
+                assert small >= 100                                                     # halves with few or no records
+    u13 = by["half-c13-n3001"].used()
+    assert (u13["W"], u13["NG"], u13["gshift"], u13["gshift_narrow"], u13["r"]) == (10, 8, 9, 8, 8)
+    u16 = by["half-c16-n3001"].used()
+    assert (u16["W"], u16["B"], u16["NG"], u16["B"] // u16["NG"]) == (8, 1 << 15, 32, GS_MAXBG)
+    for name in ("half-zero-n3001", "half-zero-n1"):
+        assert all(s["counts"].sum() == 0 for s in by[name].expected())
+    long_ = by["half-long-slice"]
+    assert long_.used()["nblk"] == 3 and long_.slice > 2 * 4096 and long_.slice % 4096 and (long_.n - 2 * long_.slice) % 4096 == 77
+    s0 = gr.split(_random_scalars(5, 1, 255)[0])
+    assert max(s0.k1, s0.k2) < 1 << 127
+
+
 def test_shape_of_the_table_cases():
     for case, ng, bg in zip(TABLE_ONLY, (1, 2, 256, 1024), (128, 64, 16, 4)):
         u = case.used(1)
@@ -350,6 +446,7 @@ def test_probe_symbol_is_exported_and_the_abi_version_stays():
     from constantine_amd import _lib
     L = _lib.lib()
     assert "ctt_hip_sort_probe" in _lib.exported_symbols() and hasattr(L, "ctt_hip_sort_probe")
+    assert "ctt_hip_sort_probe_words" in _lib.exported_symbols() and hasattr(L, "ctt_hip_sort_probe_words")
     assert L.ctt_hip_msm_abi_version() == _lib.ABI_VERSION == 11
 
 
@@ -365,6 +462,11 @@ def test_without_a_device_the_probe_refuses():
     assert L.ctt_hip_sort_probe(None, p[0], 1, p[1], p[2], p[3], p[4], p[5], p[6]) == -1
     assert L.ctt_hip_last_error() == -3
     assert all(bytes(a) == bytes([0xAB]) * len(a) for a in bufs)
+    for kwords in (4, 8):
+        L.ctt_hip_clear_last_error()
+        assert L.ctt_hip_sort_probe_words(None, p[0], kwords, 1, p[1], p[2], p[3], p[4], p[5], p[6]) == -1
+        assert L.ctt_hip_last_error() == -3
+        assert all(bytes(a) == bytes([0xAB]) * len(a) for a in bufs)
 
 
 # --- GPU -------------------------------------------------------------------------------------------------------------------------------
@@ -407,14 +509,14 @@ def _run(torch, dev, case, merged, staged, xcd, d_words):
     used = case.used(merged)
     buf = _Buffers(torch, used, ZERO_BYTES)
     e, b, m, z = buf.views()
-    got = dev.sort_probe(d_words, case.n, e, b, m, z, log2_ng=case.log2_ng, staged=staged, xcd_map=xcd, **case.sizing(merged))
+    got = dev.sort_probe(d_words, case.n, e, b, m, z, log2_ng=case.log2_ng, kwords=case.kwords, staged=staged, xcd_map=xcd, **case.sizing(merged))
     assert got == used, (case, merged, staged, xcd, got, used)
     return buf.host(), used
 
 
 def _run_and_check(dev, case, forms):
     import torch
-    d_words = torch.from_numpy(case.words.view(np.int32)).cuda()
+    d_words = torch.from_numpy(case.device_words().view(np.int32)).cuda()
     for merged in forms:
         exp = case.expected(merged)
         for staged, xcd in case.variants:
@@ -443,6 +545,36 @@ def test_sort_probe_thresholds_of_pass_b_gpu(case, dev):
 @pytest.mark.parametrize("case", TABLE_ONLY, ids=repr)
 def test_sort_probe_table_form_gpu(case, dev):
     _run_and_check(dev, case, (1,))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", HALF, ids=repr)
+def test_sort_probe_half_scalars_gpu(case, dev):
+    """case 8: 4-word scalars, the plain form over both scatter forms and both block maps"""
+    _run_and_check(dev, case, (0,))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("c, lg", [(16, 5), (13, 3)])
+def test_sort_probe_half_scalars_outside_the_contract_gpu(c, lg, dev):
+    """half scalars with bit 127 set (the plan is made for 127 bits): the same four promises as for 8-word scalars below"""
+    import torch
+    rng = random.Random(82 + c)
+    ks = [rng.randrange(1 << 127) | 1 << 127 for _ in range(1500)] + [(1 << 128) - 1, 1 << 127, (1 << 128) - 1, 1 << 127]
+    case = Case("half-outside", ks, HALF_BITS, c, lg, kwords=4)
+    lay = sr.window_layout(HALF_BITS, c)
+    val, _ = sr.digits(case.words, lay)
+    d_words = torch.from_numpy(case.device_words().view(np.int32)).cuda()
+    for staged, xcd in VARIANTS:
+        out, u = _run(torch, dev, case, 0, staged, xcd, d_words)
+        sr.check_guards(out, u, ZERO_BYTES)
+        for r in range(u["W"]):
+            bs = out["bstart"][r * (u["B"] + 1):(r + 1) * (u["B"] + 1)].astype(np.int64)
+            assert bs[0] == 0 and (np.diff(bs) >= 0).all(), (r, staged, xcd)
+            assert bs[-1] == int((val[r] > 0).sum()), (r, staged, xcd)
+            ent = out["entries"][r * case.n:r * case.n + bs[-1]]
+            assert ((ent & 0x7FFFFFFF) < case.n).all(), (r, staged, xcd)
+        assert (out["maxcount"][1:4] == 0).all()
 
 
 @pytest.mark.gpu
@@ -481,7 +613,10 @@ def _refusals(n):
             ("cap + big beyond the LDS", n, dict(ok, cap=GS_LDS_WORDS - 1024, big=1024)),
             ("more than 1024 buckets per group", n, dict(ok, c=13, log2_ng=1)),
             ("more than 16384 groups", n, dict(ok, c=20, log2_ng=15)),
-            ("a record above 32 bits", big_n, dict(ok, c=13, log2_ng=10))]
+            ("a record above 32 bits", big_n, dict(ok, c=13, log2_ng=10)),
+            ("scalars of 5 words", n, dict(ok, kwords=5)), ("scalars of 0 words", n, dict(ok, kwords=0)),
+            ("4 words under windows that end above bit 128", n, dict(ok, kwords=4)),
+            ("4 words under windows over 129 bits", n, dict(ok, kwords=4, bits=128, c=16, log2_ng=5))]
 
 
 @pytest.mark.gpu
@@ -499,7 +634,8 @@ def test_sort_probe_refusals_gpu(dev):
         L.ctt_hip_clear_last_error()
         assert dev.sort_probe(d_words, n, e, b, m, z, **sizing) is None, what
         assert L.ctt_hip_last_error() != 0 and L.ctt_hip_last_error_message(), what
-        if what in ("cap + big beyond the LDS", "more than 1024 buckets per group", "more than 16384 groups", "a record above 32 bits"):
+        if what in ("cap + big beyond the LDS", "more than 1024 buckets per group", "more than 16384 groups", "a record above 32 bits",
+                    "4 words under windows that end above bit 128", "4 words under windows over 129 bits"):
             assert b"launcher" in L.ctt_hip_last_error_message(), what      # the predicate of launch_digits_sort, not its abort
         assert buf.untouched(), what
     # a buffer smaller than the derived shape, and NULL pointers
