@@ -162,6 +162,12 @@ __global__ void __launch_bounds__(ACCUM_BLOCK, (sizeof(XYZZ<F>) > 256 ? 1 : CTT_
   }
 #endif
   if constexpr (F::UNSAT && !IsFp2<F>::value) {   // (not the quadratic extension: msm_bodies.h accum_body_z has the measurement)
+    // The hand-over.  VALU issue between the two waves of a SIMD goes by priority, then age: at equal priority the older wave runs at a lone
+    // wave's speed and is gone at half time, and the younger runs the second half ALONE, with nobody to fill the slots it leaves while it is
+    // parked on s_waitcnt.  So a wave starts at priority 1 and drops to 0 `handover` iterations before its end (accum_body_xyzz): the older
+    // wave yields there, the younger -- still at 1 -- catches up to its own drop point, and both finish together.  Below the 3 of the narrow
+    // reduction passes (k_pyr_quad).  A range shorter than the drop distance never raises.
+    if (a.handover != 0 && a.handover < a.K) __builtin_amdgcn_s_setprio(1);
     __shared__ uint4 stage[GatherLds<F>::NCH][ACCUM_BLOCK];
     GatherLds<F> gq{stage};
     accum_body<F, GatherLds<F>, INTO>(a, blockIdx.y, blockIdx.x * blockDim.x + threadIdx.x, gq);

@@ -350,6 +350,7 @@ struct MsmEngine {
     bk.stage_begin(sl, ST_ACCUM);
     st.d_buckets = d_buckets;
     AccumArgs<FD> aa{sa.entries, st.d_bstart, d_points, record_stride(), d_buckets, st.d_heads, st.d_tails, st.d_hkey, st.d_tkey, p.nent, B, p.K, p.G};
+    aa.handover = accum_handover(p);
     bk.template launch_accum<FD>(aa, W, into);
     bk.accum_mark(front_side);          // (what the next small MSM's front stage waits for: the shared entry list and records are free again)
     bk.stage_end(sl, ST_ACCUM);
@@ -467,6 +468,14 @@ struct MsmEngine {
   static double tail_free_cost_ratio() {
     static const double v = env_double("CTT_HIP_MSM_TAIL_FREE_RATIO", 0.5);
     return v;
+  }
+
+  // Drop distance of the accumulate kernel's priority hand-over for this plan (hip_backend.h k_accum), 0 = none.  By the curve's measurement
+  // (msm_bodies.h ACCUM_HANDOVER, ACCUM_HANDOVER_LOG2N) unless the option names a distance: K / 8, and not below the curve's floor.
+  uint32_t accum_handover(const MsmPlan& p) const {
+    if (opt.accum_handover >= 2) return (uint32_t)opt.accum_handover;
+    if (opt.accum_handover != 1 || C::ACCUM_HANDOVER == 0 || p.pairs() < (1u << C::ACCUM_HANDOVER_LOG2N)) return 0u;
+    return p.K / 8u > (uint32_t)C::ACCUM_HANDOVER ? p.K / 8u : (uint32_t)C::ACCUM_HANDOVER;
   }
 
   int claim_slot(uint32_t n) {

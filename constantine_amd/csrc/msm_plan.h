@@ -75,6 +75,9 @@ struct MsmOptions {
   // the endomorphism split of a device-resident MSM (curves that have one: msm_bodies.h GlvOf): 0 = at the curve's sizes (GLV_LOG2N .. GLV_MAX_LOG2N),
   // 1 = at every size, 2 = never.  Option "glv", $CTT_HIP_MSM_GLV.
   int glv = 0;
+  // the priority hand-over of the accumulate kernel (hip_backend.h k_accum): 0 = off (no priority instruction runs), 1 = the curve's drop distance at the
+  // curve's sizes (msm_bodies.h Curve::ACCUM_HANDOVER, ACCUM_HANDOVER_LOG2N; msm_pipeline.h accum_handover), n >= 2 = this drop distance at every size.  Option "accum_handover", $CTT_HIP_MSM_ACCUM_HANDOVER.
+  int accum_handover = 1;
 };
 
 // The sort's shipped constants: the floor of a partition slice, pass B's LDS tile (cap) and the bucket size above which its LDS image is

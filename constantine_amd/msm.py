@@ -128,7 +128,8 @@ class DeviceMsm:
         """ctt_hip_msm_set_option: "c", "K", "S", "chunks", "horner_bits", "host_window_sums", "sort_staged", "sort_xcd", "timings", "timings_every",
         and the forms of the head merge and the stream placements of a pipelined MSM: "merge_chain", "merge_lmax", "merge_queue_quad",
         "early_tail" (default 1), "front_side", "pyr0_tail", and "glv" -- the endomorphism split of BLS12-381 G1: 0 at the curve's measured
-        sizes, 1 always, 2 never -- (include/ctt_msm_hip.h); 0 = automatic / off.  KeyError for an unknown key."""
+        sizes, 1 always, 2 never --, "accum_handover" -- the priority hand-over of the accumulate kernel: 0 off, 1 the curve's drop distance
+        (default), n >= 2 that distance -- (include/ctt_msm_hip.h); 0 = automatic / off.  KeyError for an unknown key."""
         if self.L.ctt_hip_msm_set_option(self.ctx, key.encode(), int(value)) != 0:
             raise KeyError(key)
 

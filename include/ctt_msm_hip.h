@@ -193,7 +193,9 @@ void ctt_hip_msm_ctx_destroy(ctt_hip_msm_ctx* ctx);
  * pass of a pipelined MSM on the tail stream (0 never, 1 automatic -- the default --, 2 whenever pipelining); "front_side"
  * conversion and sort of a pipelined MSM on the front stream (1 whenever pipelining, 2 never); "pyr0_tail" 1 = the first reduction
  * pass of a small MSM on the tail stream; "glv" the endomorphism split of a device-resident BLS12-381 G1 MSM (0 at the curve's
- * measured sizes, 1 at every size, 2 never; also $CTT_HIP_MSM_GLV).  A context also reads $CTT_HIP_MSM_MERGE_CHAIN, $CTT_HIP_MSM_MERGE_LMAX and
+ * measured sizes, 1 at every size, 2 never; also $CTT_HIP_MSM_GLV); "accum_handover" the priority hand-over between the waves of the
+ * accumulate kernel (0 off, 1 the curve's drop distance -- the default --, n >= 2 this many iterations before a wave's end; also
+ * $CTT_HIP_MSM_ACCUM_HANDOVER): it moves when the kernel's waves issue, never what they compute.  A context also reads $CTT_HIP_MSM_MERGE_CHAIN, $CTT_HIP_MSM_MERGE_LMAX and
  * $CTT_HIP_MSM_QUAD (reduction passes of at most this many additions run with four lanes per addition) when it is created.
  * A context created with $CTT_HIP_CU_TAIL = r > 0 partitions the chip: its tail stream runs on r compute units of every XCD
  * (hipExtStreamCreateWithCUMask), its main stream on the others -- an experiment of round 6, measured slower than sharing the chip

@@ -38,6 +38,11 @@ def main():
                          ("SQ_WAIT_ANY", "parked on s_waitcnt (gather, bucket_start loads)")):
             if k in v:
                 print(f"#   {label}: {100 * v[k] / wc:.1f}% of wave cycles")
+    if wc and v.get("SQ_WAVES") and v.get("GRBM_GUI_ACTIVE"):
+        # SQ_WAVE_CYCLES counts in units of four cycles, GRBM_GUI_ACTIVE is summed over the 8 XCDs.  Waves that start together with equal
+        # work should all live for the whole kernel (share ~ 1); 0.75 = one wave of each SIMD gone at half time (EXPERIMENTS.md R8.1)
+        print(f"#   mean wave lifetime: SQ_WAVE_CYCLES x 4 / (SQ_WAVES x GRBM_GUI_ACTIVE / 8 XCDs) = "
+              f"{wc * 4 / (v['SQ_WAVES'] * v['GRBM_GUI_ACTIVE'] / 8):.3f} of the kernel")
     if "SQ_INSTS_VALU" in v and madds > 0:
         print(f"#   VALU wave-instructions per launch {v['SQ_INSTS_VALU']:.4g} = {v['SQ_INSTS_VALU'] * 64 / madds:.0f} per mixed addition (one lane)")
     if "SQ_INSTS_SALU" in v and madds > 0:

@@ -2,7 +2,7 @@
 
     python tools/sweep.py <curve> <log2n> key=v1,v2,... [key=...] [-- <curve> <log2n> key=...]
 
-keys are engine options (c, K, reduce_block, horner_bits, quad_ratio, host_window_sums); the cartesian product of the value
+keys are engine options (c, K, horner_bits, host_window_sums, glv, accum_handover, ...); the cartesian product of the value
 lists is measured: ms per MSM with two in flight, median blocking latency, stage times of one blocking call.  One JSON line
 per configuration; `same` = the result equals the first configuration's of that (curve, size)."""
 import itertools
