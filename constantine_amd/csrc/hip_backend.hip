@@ -78,6 +78,36 @@ __device__ __forceinline__ uint32_t part_slice_of_block(const SortArgs& a, uint3
   const uint32_t q = nblk >> 3, r = nblk & 7u, x = b & 7u;
   return x * q + (x < r ? x : r) + (b >> 3);
 }
+// The pair forms (msm_bodies.h sort_by_pairs): a thread holds PP_NS pairs of half scalars -- pair p = halves p and n/2 + p, the entries
+// of the same numbers -- and walks both halves of each (for_each_digit_pair): 2 x PP_NS records per window step, the registers of PP_NS
+// whole scalars.  A slice of `slice` half scalars is slice / 2 pairs: 2048 of them for the 512 blocks of a large MSM, two per lane.
+#ifndef CTT_SORT_PAIR_NS
+#define CTT_SORT_PAIR_NS 2
+#endif
+static constexpr int PP_NS = CTT_SORT_PAIR_NS;
+template <int NS>
+__device__ __forceinline__ void load_pairs(const SortArgs& a, uint32_t pb, uint32_t p1, uint32_t (&k)[NS][8]) {
+  const uint4* sc = reinterpret_cast<const uint4*>(a.scalars);
+  const uint32_t np = a.n >> 1;
+#pragma unroll
+  for (int s = 0; s < NS; s++) {
+    const uint32_t p = pb + (uint32_t)s * blockDim.x + threadIdx.x;
+    uint4 lo = make_uint4(0u, 0u, 0u, 0u), hi = lo;   // a zero pair has no digits: no records
+    if (p < p1) {
+      lo = sc[p];
+      hi = sc[(uint64_t)np + p];
+    }
+    k[s][0] = lo.x; k[s][1] = lo.y; k[s][2] = lo.z; k[s][3] = lo.w;
+    k[s][4] = hi.x; k[s][5] = hi.y; k[s][6] = hi.z; k[s][7] = hi.w;
+  }
+}
+// the pairs [p0, p1) of slice blk
+__device__ __forceinline__ void pair_slice(const SortArgs& a, uint32_t blk, uint32_t& p0, uint32_t& p1) {
+  const uint32_t hs = a.slice >> 1, np = a.n >> 1;
+  p0 = blk * hs < np ? blk * hs : np;
+  p1 = (np - p0 > hs) ? p0 + hs : np;
+}
+template <bool PAIR>
 __global__ void __launch_bounds__(512) k_part_count(SortArgs a, uint32_t w0, uint32_t nw) {
   extern __shared__ uint32_t lds[];
   const uint32_t ncnt = a.merged ? a.NG : nw * a.NG;  // merged: every digit window counts into the one set of groups
@@ -88,16 +118,31 @@ __global__ void __launch_bounds__(512) k_part_count(SortArgs a, uint32_t w0, uin
   if (blockIdx.x == 0 && w0 == 0 && threadIdx.x < 4) a.maxcount[threadIdx.x] = 0;
   __syncthreads();
   const uint32_t blk = part_slice_of_block(a, blockIdx.x, gridDim.x);
-  const uint32_t j0 = blk * a.slice;
-  const uint32_t j1 = (j0 + a.slice < a.n) ? j0 + a.slice : a.n;
-  for (uint32_t jb = j0; jb < j1; jb += PA_NS * blockDim.x) {
-    uint32_t k[PA_NS][8];
-    load_scalars<PA_NS>(a, jb, j1, k);
-    for_each_digit<PA_NS>(k, w0, nw, a.lay, [&](uint32_t w, const uint32_t (&d)[PA_NS]) {
+  auto count = [&](uint32_t w, const auto& d) {
+    constexpr int NR = (int)std::extent<std::remove_reference_t<decltype(d)>>::value;
 #pragma unroll
-      for (int s = 0; s < PA_NS; s++)
-        if (d[s] != DIGIT_NONE) atomicAdd(&lds[(w - w0) * wstep + sort_group(a, w, d[s] >> 1)], 1u);
-    });
+    for (int s = 0; s < NR; s++)
+      if (d[s] != DIGIT_NONE) atomicAdd(&lds[(w - w0) * wstep + sort_group(a, w, d[s] >> 1)], 1u);
+  };
+  if constexpr (PAIR) {
+    uint32_t p0, p1;
+    pair_slice(a, blk, p0, p1);
+    for (uint32_t pb = p0; pb < p1; pb += PP_NS * blockDim.x) {
+      uint32_t k[PP_NS][8];
+      load_pairs<PP_NS>(a, pb, p1, k);
+      for_each_digit_pair<PP_NS>(k, w0, nw, a.lay, [&](uint32_t w, const uint32_t (&da)[PP_NS], const uint32_t (&db)[PP_NS]) {
+        count(w, da);
+        count(w, db);
+      });
+    }
+  } else {
+    const uint32_t j0 = blk * a.slice;
+    const uint32_t j1 = (j0 + a.slice < a.n) ? j0 + a.slice : a.n;
+    for (uint32_t jb = j0; jb < j1; jb += PA_NS * blockDim.x) {
+      uint32_t k[PA_NS][8];
+      load_scalars<PA_NS>(a, jb, j1, k);
+      for_each_digit<PA_NS>(k, w0, nw, a.lay, [&](uint32_t w, const uint32_t (&d)[PA_NS]) { count(w, d); });
+    }
   }
   __syncthreads();
   uint32_t* out = a.cntA + (uint64_t)blk * (a.W * a.NG) + (uint64_t)(a.merged ? 0u : w0) * a.NG;
@@ -173,8 +218,10 @@ __global__ void __launch_bounds__(1024) k_scan_u32(const uint32_t* __restrict__ 
 // NG runs of ONE window: the partially written lines are few and complete within a few hundred cycles (emitting all W
 // records of a scalar at once kept W*NG runs open per block -- 8x the L2 at N = 2^22, 0.71 ms).  Round 2: the scalars used to
 // be staged in LDS as [scalar][8 words], which made every digit two 16-way bank-conflicted LDS reads.
-template <bool MERGED>   // two instantiations: the table-less form keeps its register count (two workgroups per CU)
+// PAIR: the slice is walked pair by pair (load_pairs above); records 0 .. PP_NS-1 of a step are the first halves, the others the second.
+template <bool MERGED, bool PAIR = false>   // the table-less form keeps its register count (two workgroups per CU)
 __global__ void __launch_bounds__(1024) k_part_scatter(SortArgs a, uint32_t w0, uint32_t nw) {
+  static_assert(!(MERGED && PAIR), "half scalars have no window table");
   extern __shared__ uint32_t lds[];
   const uint32_t ncnt = MERGED ? a.NG : nw * a.NG;
   const uint32_t wstep = MERGED ? 0u : a.NG;
@@ -187,39 +234,60 @@ __global__ void __launch_bounds__(1024) k_part_scatter(SortArgs a, uint32_t w0, 
     cur[i] = off[i] + a.gbase[(uint64_t)(set0 + w) * (a.NG + 1) + g];
   }
   __syncthreads();
-  const uint32_t j0 = blk * a.slice;
-  const uint32_t j1 = (j0 + a.slice < a.n) ? j0 + a.slice : a.n;
   const uint32_t sh = a.jbits + 1u;
-  for (uint32_t jb = j0; jb < j1; jb += PS_NS * blockDim.x) {
-    uint32_t k[PS_NS][8];
-    load_scalars<PS_NS>(a, jb, j1, k);
-    for_each_digit<PS_NS>(k, w0, nw, a.lay, [&](uint32_t w, const uint32_t (&d)[PS_NS]) {
-      // the waves of the block move from window to window together (w is uniform over the block): the runs a block has open
-      // at any moment are those of ONE window, and their partially written lines complete while they are still in the L2
-      __syncthreads();
-      uint32_t* cw = cur + (w - w0) * wstep;
-      const uint32_t gmask = (1u << sort_gshift(a, w)) - 1u;
+  // one window step of the block: d[] the digits of the NR records a lane holds, id_of(s) their entries
+  auto step = [&](uint32_t w, const auto& d, auto&& id_of) {
+    constexpr int NR = (int)std::extent<std::remove_reference_t<decltype(d)>>::value;
+    // the waves of the block move from window to window together (w is uniform over the block): the runs a block has open
+    // at any moment are those of ONE window, and their partially written lines complete while they are still in the L2
+    __syncthreads();
+    uint32_t* cw = cur + (w - w0) * wstep;
+    const uint32_t gmask = (1u << sort_gshift(a, w)) - 1u;
+    // claim the NR positions first, store afterwards: a store issued between two claims makes the next claim's
+    // address / data registers wait for it (s_waitcnt vmcnt(0) per record: 383 -> 588 us at 2^22 when it was written so)
+    uint32_t pos[NR];
+#pragma unroll
+    for (int s = 0; s < NR; s++) pos[s] = d[s] != DIGIT_NONE ? atomicAdd(&cw[sort_group(a, w, d[s] >> 1)], 1u) : 0u;
+    if constexpr (MERGED) {  // window table: 64-bit records, the entry is the table row w*id_stride + j
+      uint64_t* pw = reinterpret_cast<uint64_t*>(a.part);
+#pragma unroll
+      for (int s = 0; s < NR; s++)
+        if (d[s] != DIGIT_NONE)
+          pw[pos[s]] = ((uint64_t)((d[s] >> 1) & gmask) << 32) | ((d[s] & 1u) << 31) | (w * a.id_stride + id_of(s));
+    } else {
+      uint32_t* pw = a.part + (uint64_t)w * a.nent;
+#pragma unroll
+      for (int s = 0; s < NR; s++)
+        if (d[s] != DIGIT_NONE)
+          pw[pos[s]] = (((d[s] >> 1) & gmask) << sh) | ((d[s] & 1u) << a.jbits) | id_of(s);
+    }
+  };
+  if constexpr (PAIR) {
+    uint32_t p0, p1;
+    pair_slice(a, blk, p0, p1);
+    const uint32_t np = a.n >> 1;
+    for (uint32_t pb = p0; pb < p1; pb += PP_NS * blockDim.x) {
+      uint32_t k[PP_NS][8];
+      load_pairs<PP_NS>(a, pb, p1, k);
+      const uint32_t id0 = pb + threadIdx.x;
+      for_each_digit_pair<PP_NS>(k, w0, nw, a.lay, [&](uint32_t w, const uint32_t (&da)[PP_NS], const uint32_t (&db)[PP_NS]) {
+        uint32_t d[2 * PP_NS];
+#pragma unroll
+        for (int s = 0; s < PP_NS; s++) { d[s] = da[s]; d[PP_NS + s] = db[s]; }
+        step(w, d, [&](int s) { return (s < PP_NS ? id0 : np + id0) + (uint32_t)(s < PP_NS ? s : s - PP_NS) * blockDim.x; });
+      });
+    }
+  } else {
+    const uint32_t j0 = blk * a.slice;
+    const uint32_t j1 = (j0 + a.slice < a.n) ? j0 + a.slice : a.n;
+    for (uint32_t jb = j0; jb < j1; jb += PS_NS * blockDim.x) {
+      uint32_t k[PS_NS][8];
+      load_scalars<PS_NS>(a, jb, j1, k);
       const uint32_t id0 = jb + threadIdx.x;
-      // claim the PS_NS positions first, store afterwards: a store issued between two claims makes the next claim's
-      // address / data registers wait for it (s_waitcnt vmcnt(0) per record: 383 -> 588 us at 2^22 when it was written so)
-      uint32_t pos[PS_NS];
-#pragma unroll
-      for (int s = 0; s < PS_NS; s++) pos[s] = d[s] != DIGIT_NONE ? atomicAdd(&cw[sort_group(a, w, d[s] >> 1)], 1u) : 0u;
-      if constexpr (MERGED) {  // window table: 64-bit records, the entry is the table row w*id_stride + j
-        uint64_t* pw = reinterpret_cast<uint64_t*>(a.part);
-        const uint32_t row0 = w * a.id_stride + id0;
-#pragma unroll
-        for (int s = 0; s < PS_NS; s++)
-          if (d[s] != DIGIT_NONE)
-            pw[pos[s]] = ((uint64_t)((d[s] >> 1) & gmask) << 32) | ((d[s] & 1u) << 31) | (row0 + (uint32_t)s * blockDim.x);
-      } else {
-        uint32_t* pw = a.part + (uint64_t)w * a.nent;
-#pragma unroll
-        for (int s = 0; s < PS_NS; s++)
-          if (d[s] != DIGIT_NONE)
-            pw[pos[s]] = (((d[s] >> 1) & gmask) << sh) | ((d[s] & 1u) << a.jbits) | (id0 + (uint32_t)s * blockDim.x);
-      }
-    });
+      for_each_digit<PS_NS>(k, w0, nw, a.lay, [&](uint32_t w, const uint32_t (&d)[PS_NS]) {
+        step(w, d, [&](int s) { return id0 + (uint32_t)s * blockDim.x; });
+      });
+    }
   }
 }
 
@@ -231,11 +299,13 @@ __global__ void __launch_bounds__(1024) k_part_scatter(SortArgs a, uint32_t w0, 
 // 2^22 pairs, 16 bytes at 2^24), a wave's store instruction touches a handful of lines, and the piece of a line arrives in one go.
 // The block's write cursors live in its own row of cntA (advanced in place by the lane that owns the group): no LDS for
 // W x NG cursors, so one launch walks all windows.  NG <= 1024 (one group per lane in the scan); beyond that the direct form runs.
-template <bool MERGED>
+template <bool MERGED, bool PAIR = false>   // PAIR: as in k_part_scatter
 __global__ void __launch_bounds__(1024) k_part_scatter_staged(SortArgs a) {
+  static_assert(!(MERGED && PAIR), "half scalars have no window table");
   extern __shared__ uint32_t lds[];
   using R = typename std::conditional<MERGED, uint64_t, uint32_t>::type;
-  constexpr uint32_t STEP = PS_NS * 1024u;
+  constexpr int NR = PAIR ? 2 * PP_NS : PS_NS;   // records a lane holds per window step
+  constexpr uint32_t STEP = (uint32_t)NR * 1024u;
   const uint32_t NG = a.NG;
   uint32_t* hist = lds;                 // [NG] records of the current (step, window) per group
   uint32_t* lbase = hist + NG;          // [NG] first slot of the group in the stage
@@ -250,64 +320,85 @@ __global__ void __launch_bounds__(1024) k_part_scatter_staged(SortArgs a) {
     for (uint32_t set = 0; set < a.W; set++) cursor[set * NG + tid] += a.gbase[(uint64_t)set * (NG + 1) + tid];
     hist[tid] = 0;
   }
-  const uint32_t j0 = blk * a.slice;
-  const uint32_t j1 = (j0 + a.slice < a.n) ? j0 + a.slice : a.n;
   const uint32_t sh = a.jbits + 1u;
-  for (uint32_t jb = j0; jb < j1; jb += STEP) {
-    uint32_t k[PS_NS][8];
-    load_scalars<PS_NS>(a, jb, j1, k);
-    for_each_digit<PS_NS>(k, 0u, a.Wd, a.lay, [&](uint32_t w, const uint32_t (&d)[PS_NS]) {
-      const uint32_t set = MERGED ? 0u : w;
-      const uint32_t gmask = (1u << sort_gshift(a, w)) - 1u;
-      const uint32_t id0 = jb + tid;
-      __syncthreads();   // the previous flush has read the stage; hist is zero again
-      uint32_t g[PS_NS], rk[PS_NS];
+  // one window step of the block: d[] the digits of the NR records a lane holds, id_of(s) their entries
+  auto step = [&](uint32_t w, const uint32_t (&d)[NR], auto&& id_of) {
+    const uint32_t set = MERGED ? 0u : w;
+    const uint32_t gmask = (1u << sort_gshift(a, w)) - 1u;
+    __syncthreads();   // the previous flush has read the stage; hist is zero again
+    uint32_t g[NR], rk[NR];
 #pragma unroll
-      for (int s = 0; s < PS_NS; s++) {
-        g[s] = d[s] != DIGIT_NONE ? sort_group(a, w, d[s] >> 1) : 0u;
-        rk[s] = d[s] != DIGIT_NONE ? atomicAdd(&hist[g[s]], 1u) : 0u;
-      }
-      __syncthreads();
-      const uint32_t v = tid < NG ? hist[tid] : 0u;
-      uint32_t x = v;
+    for (int s = 0; s < NR; s++) {
+      g[s] = d[s] != DIGIT_NONE ? sort_group(a, w, d[s] >> 1) : 0u;
+      rk[s] = d[s] != DIGIT_NONE ? atomicAdd(&hist[g[s]], 1u) : 0u;
+    }
+    __syncthreads();
+    const uint32_t v = tid < NG ? hist[tid] : 0u;
+    uint32_t x = v;
 #pragma unroll
-      for (uint32_t o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-      }
-      if (lane == 63) wsum[wv] = x;
-      __syncthreads();
-      uint32_t base = x - v, total = 0;
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+      const uint32_t y = __shfl_up(x, o, 64);
+      if (lane >= o) x += y;
+    }
+    if (lane == 63) wsum[wv] = x;
+    __syncthreads();
+    uint32_t base = x - v, total = 0;
 #pragma unroll
-      for (uint32_t q = 0; q < 16; q++) {
-        const uint32_t t = wsum[q];
-        if (q < wv) base += t;
-        total += t;
-      }
-      if (tid < NG) {
-        lbase[tid] = base;
-        uint32_t* cp = cursor + set * NG + tid;
-        const uint32_t gp = *cp;
-        gposd[tid] = gp - base;
-        *cp = gp + v;
-        hist[tid] = 0;
-      }
-      __syncthreads();
+    for (uint32_t q = 0; q < 16; q++) {
+      const uint32_t t = wsum[q];
+      if (q < wv) base += t;
+      total += t;
+    }
+    if (tid < NG) {
+      lbase[tid] = base;
+      uint32_t* cp = cursor + set * NG + tid;
+      const uint32_t gp = *cp;
+      gposd[tid] = gp - base;
+      *cp = gp + v;
+      hist[tid] = 0;
+    }
+    __syncthreads();
 #pragma unroll
-      for (int s = 0; s < PS_NS; s++)
-        if (d[s] != DIGIT_NONE) {
-          const uint32_t slot = lbase[g[s]] + rk[s];
-          stage_g[slot] = (uint16_t)g[s];
-          if constexpr (MERGED) {
-            stage_rec[slot] = ((uint64_t)((d[s] >> 1) & gmask) << 32) | ((d[s] & 1u) << 31) | (w * a.id_stride + id0 + (uint32_t)s * 1024u);
-          } else {
-            stage_rec[slot] = (((d[s] >> 1) & gmask) << sh) | ((d[s] & 1u) << a.jbits) | (id0 + (uint32_t)s * 1024u);
-          }
+    for (int s = 0; s < NR; s++)
+      if (d[s] != DIGIT_NONE) {
+        const uint32_t slot = lbase[g[s]] + rk[s];
+        stage_g[slot] = (uint16_t)g[s];
+        if constexpr (MERGED) {
+          stage_rec[slot] = ((uint64_t)((d[s] >> 1) & gmask) << 32) | ((d[s] & 1u) << 31) | (w * a.id_stride + id_of(s));
+        } else {
+          stage_rec[slot] = (((d[s] >> 1) & gmask) << sh) | ((d[s] & 1u) << a.jbits) | id_of(s);
         }
-      __syncthreads();
-      R* pw = reinterpret_cast<R*>(a.part) + (MERGED ? 0ull : (uint64_t)w * a.nent);
-      for (uint32_t i = tid; i < total; i += 1024u) pw[gposd[stage_g[i]] + i] = stage_rec[i];
-    });
+      }
+    __syncthreads();
+    R* pw = reinterpret_cast<R*>(a.part) + (MERGED ? 0ull : (uint64_t)w * a.nent);
+    for (uint32_t i = tid; i < total; i += 1024u) pw[gposd[stage_g[i]] + i] = stage_rec[i];
+  };
+  if constexpr (PAIR) {
+    uint32_t p0, p1;
+    pair_slice(a, blk, p0, p1);
+    const uint32_t np = a.n >> 1;
+    for (uint32_t pb = p0; pb < p1; pb += PP_NS * 1024u) {
+      uint32_t k[PP_NS][8];
+      load_pairs<PP_NS>(a, pb, p1, k);
+      const uint32_t id0 = pb + tid;
+      for_each_digit_pair<PP_NS>(k, 0u, a.Wd, a.lay, [&](uint32_t w, const uint32_t (&da)[PP_NS], const uint32_t (&db)[PP_NS]) {
+        uint32_t d[NR];
+#pragma unroll
+        for (int s = 0; s < PP_NS; s++) { d[s] = da[s]; d[PP_NS + s] = db[s]; }
+        step(w, d, [&](int s) { return (s < PP_NS ? id0 : np + id0) + (uint32_t)(s < PP_NS ? s : s - PP_NS) * 1024u; });
+      });
+    }
+  } else {
+    const uint32_t j0 = blk * a.slice;
+    const uint32_t j1 = (j0 + a.slice < a.n) ? j0 + a.slice : a.n;
+    for (uint32_t jb = j0; jb < j1; jb += STEP) {
+      uint32_t k[PS_NS][8];
+      load_scalars<PS_NS>(a, jb, j1, k);
+      const uint32_t id0 = jb + tid;
+      for_each_digit<PS_NS>(k, 0u, a.Wd, a.lay, [&](uint32_t w, const uint32_t (&d)[PS_NS]) {
+        step(w, d, [&](int s) { return id0 + (uint32_t)s * 1024u; });
+      });
+    }
   }
 }
 
@@ -571,9 +662,13 @@ void HipBackend::launch_digits_sort(const SortArgs& a) {
   uint32_t wb = a.merged ? a.Wd : 16384u / a.NG;
   if (wb < 1) wb = 1;
   if (wb > a.Wd) wb = a.Wd;
+  // half scalars: the slices are walked pair by pair (msm_bodies.h sort_by_pairs)
+  const bool pair = sort_by_pairs(a);
   for (uint32_t w0 = 0; w0 < a.Wd; w0 += wb) {
     const uint32_t nw = (w0 + wb <= a.Wd) ? wb : a.Wd - w0;
-    hipLaunchKernelGGL(k_part_count, dim3(a.nblk), dim3(512), (a.merged ? a.NG : (size_t)nw * a.NG) * 4, front(), a, w0, nw);
+    const size_t lds_bytes = (a.merged ? a.NG : (size_t)nw * a.NG) * 4;
+    if (pair) hipLaunchKernelGGL(k_part_count<true>, dim3(a.nblk), dim3(512), lds_bytes, front(), a, w0, nw);
+    else hipLaunchKernelGGL(k_part_count<false>, dim3(a.nblk), dim3(512), lds_bytes, front(), a, w0, nw);
     HIP_CHECK(hipGetLastError());
   }
   hipLaunchKernelGGL(k_part_scan_blocks, dim3((ncol + SCAN_CX - 1) / SCAN_CX), dim3(1024), 0, front(), a.cntA, a.gtot, ncol, a.nblk);
@@ -583,14 +678,16 @@ void HipBackend::launch_digits_sort(const SortArgs& a) {
   if (a.staged && a.NG <= 1024u && (a.NG & (a.NG - 1u)) == 0u) {
     // one launch over all windows: records staged through LDS and written piece by piece (k_part_scatter_staged)
     const size_t rec = a.merged ? 8 : 4;
-    const size_t lds_bytes = ((size_t)3 * a.NG + 16) * 4 + (size_t)PS_NS * 1024 * (2 + rec);
+    const size_t lds_bytes = ((size_t)3 * a.NG + 16) * 4 + (size_t)(pair ? 2 * PP_NS : PS_NS) * 1024 * (2 + rec);
     if (a.merged) hipLaunchKernelGGL(k_part_scatter_staged<true>, dim3(a.nblk), dim3(1024), lds_bytes, front(), a);
+    else if (pair) hipLaunchKernelGGL((k_part_scatter_staged<false, true>), dim3(a.nblk), dim3(1024), lds_bytes, front(), a);
     else hipLaunchKernelGGL(k_part_scatter_staged<false>, dim3(a.nblk), dim3(1024), lds_bytes, front(), a);
     HIP_CHECK(hipGetLastError());
   } else {
     for (uint32_t w0 = 0; w0 < a.Wd; w0 += wb) {
       const uint32_t nw = (w0 + wb <= a.Wd) ? wb : a.Wd - w0;
       if (a.merged) hipLaunchKernelGGL(k_part_scatter<true>, dim3(a.nblk), dim3(1024), (size_t)a.NG * 4, front(), a, w0, nw);
+      else if (pair) hipLaunchKernelGGL((k_part_scatter<false, true>), dim3(a.nblk), dim3(1024), (size_t)nw * a.NG * 4, front(), a, w0, nw);
       else hipLaunchKernelGGL(k_part_scatter<false>, dim3(a.nblk), dim3(1024), (size_t)nw * a.NG * 4, front(), a, w0, nw);
       HIP_CHECK(hipGetLastError());
     }

@@ -150,6 +150,44 @@ CTT_HD void for_each_digit(const uint32_t (&k)[NS][8], uint32_t w0, uint32_t nw,
   }
 }
 
+// The same walk for a thread that holds PAIRS of 4-word half scalars (the endomorphism split): half A in words 0-3 of k[s], half B in
+// words 4-7 -- the registers one half scalar takes in the form above, whose upper four words it carries as zeros.  fn(w, dA[NS], dB[NS])
+// per window of a layout that ends at or below bit 128 (a window that starts above it is not visited).  Each half is recoded on its own:
+// the word above a half's word 3 reads as zero, so no bit of half B reaches half A's top window, and half B's lowest window starts with
+// the zero below bit 0 like any scalar's.  Same values as booth_digit_packed on each 4-word scalar zero-extended.
+template <int NS, class Fn>
+CTT_HD void for_each_digit_pair(const uint32_t (&k)[NS][8], uint32_t w0, uint32_t nw, const WinLayout& L, Fn&& fn) {
+  uint32_t w = w0;
+  const uint32_t wend = w0 + nw;
+#pragma unroll
+  for (int word = 0; word < 4; word++) {
+    while (w < wend) {
+      const uint32_t i = (uint32_t)L.off(w);
+      const int c = L.width(w);
+      const uint32_t mask = (1u << (c + 1)) - 1u, vmask = (1u << c) - 1u;
+      const uint32_t pos = i ? i - 1u : 0u;
+      if ((pos >> 5) != (uint32_t)word) break;
+      const uint32_t sh = pos & 31u;
+      uint32_t dg[2][NS];
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+#pragma unroll
+        for (int s = 0; s < NS; s++) {
+          const uint32_t lo = k[s][4 * h + word], hi = word < 3 ? k[s][4 * h + (word < 3 ? word + 1 : 3)] : 0u;
+          uint32_t d = i ? (uint32_t)((((uint64_t)hi << 32) | lo) >> sh) : lo << 1;
+          d &= mask;
+          const uint32_t neg = d >> c;
+          const uint32_t e = (d + 1u) >> 1;
+          const uint32_t val = (neg ? (1u << c) - e : e) & vmask;
+          dg[h][s] = val ? (((val - 1u) << 1) | neg) : DIGIT_NONE;
+        }
+      }
+      fn(w, dg[0], dg[1]);
+      w++;
+    }
+  }
+}
+
 // Digits + sort by bucket.  Output contract (what the accumulation consumes): for every bucket set r (one per window;
 // a single one for all windows in the window-table form below), entries[r][0..bucket_start[r][B]) = (point index | sign << 31)
 // of every non-zero digit, grouped by bucket in increasing bucket order (any order inside a bucket), bucket_start[r][b] =
@@ -194,6 +232,9 @@ struct SortArgs {
   // windows cover 128 bits; the sort kernels read the upper words as zero)
   uint32_t kwords = 8;
 };
+// Half scalars are partitioned by PAIR: slice blk holds the pairs [blk * slice / 2, (blk + 1) * slice / 2), that is the entries j and
+// n/2 + j of each -- one thread walks both halves of a pair (for_each_digit_pair).  Every other input is partitioned by consecutive scalars.
+CTT_HD bool sort_by_pairs(const SortArgs& a) { return a.kwords == 4u && !a.merged && (a.n & 1u) == 0u && (a.slice & 1u) == 0u; }
 
 // Fr Montgomery -> canonical (batchFromField, finite_fields.nim:915-920)
 template <class Fr>

@@ -36,6 +36,12 @@ def main(path, warm=0):
     print(f"{'kernel':72s} {'calls':>6s} {'total_us':>12s} {'avg_us':>10s} {'min_us':>10s} {'max_us':>10s} {'pct':>6s}")
     for k, v in sorted(agg.items(), key=lambda kv: -sum(kv[1])):
         print(f"{k:72s} {len(v):6d} {sum(v):12.1f} {sum(v)/len(v):10.1f} {min(v):10.1f} {max(v):10.1f} {100*sum(v)/tot:6.2f}")
+    # the stretch between two accumulations (what a pipelined MSM's front stage and the previous tail's wide passes have to fit into)
+    acc = [r for r in rows[first:] if "k_accum" in r[0]]
+    gaps = [(b[1] - a[2]) / 1e3 for a, b in zip(acc, acc[1:])]
+    if gaps:
+        gaps.sort()
+        print(f"end of one k_accum to the start of the next: {len(gaps)} gaps, median {gaps[len(gaps) // 2]:.1f} us, min {gaps[0]:.1f}, max {gaps[-1]:.1f}")
 
 
 if __name__ == "__main__":
