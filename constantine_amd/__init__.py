@@ -10,6 +10,7 @@ Only what the MSM hot path needs lives here:
             process driving several GPUs, is ctt_hip_msm_set_devices / $CTT_HIP_DEVICES (msm.set_devices)
   synth.py  synthetic benchmark inputs (seeded scalars)
   verkle.py  batched Verkle commitments over a fixed Banderwagon basis: VerkleCrs.commit, batchMapToScalarField, serializeBatch_vartime
+  ntt.py    batched NTT over a curve's scalar field (NttPlan); the EIP-7594 cells and cell proofs of kzg.py run on it
   kzg.py, evm.py  ctypes callers of the reference's KZG / EIP-2537 MSM-precompile C symbols (csrc/protocols.hip: host side in C++)
 """
 from .curves import CURVES, CurveInfo  # noqa: F401

@@ -40,7 +40,11 @@ def exported_symbols():
              "ctt_hip_eth_kzg_blob_to_scalars", "ctt_hip_eth_kzg_challenge", "ctt_hip_eth_kzg_quotient_host",
              # part 4: batched Verkle commitments over a fixed Banderwagon basis
              "ctt_hip_verkle_crs_create", "ctt_hip_verkle_crs_destroy", "ctt_hip_verkle_crs_window_bits", "ctt_hip_verkle_commit_batch",
-             "ctt_hip_banderwagon_map_to_fr_batch", "ctt_hip_banderwagon_serialize_batch", "ctt_hip_verkle_last_timings", "ctt_hip_verkle_update_batch"]
+             "ctt_hip_banderwagon_map_to_fr_batch", "ctt_hip_banderwagon_serialize_batch", "ctt_hip_verkle_last_timings", "ctt_hip_verkle_update_batch",
+             # part 5: the scalar-field NTT; the EIP-7594 cells and cell proofs on top of it (part 3)
+             "ctt_hip_fr_ntt_plan_create", "ctt_hip_fr_ntt_plan_destroy", "ctt_hip_fr_ntt_plan_info", "ctt_hip_fr_ntt",
+             "ctt_eth_kzg_compute_cells_and_kzg_proofs", "ctt_hip_eth_kzg_compute_cells", "ctt_hip_eth_kzg_cell_quotients",
+             "ctt_hip_eth_kzg_last_cell_timings"]
     return syms
 
 
@@ -252,5 +256,23 @@ def lib():
     if "ctt_hip_verkle_update_batch" not in missing:
         L.ctt_hip_verkle_update_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32]
         L.ctt_hip_verkle_update_batch.restype = i32
+    if "ctt_hip_fr_ntt" not in missing:
+        L.ctt_hip_fr_ntt_plan_create.argtypes = [vp, i32, i32, vp, i32]
+        L.ctt_hip_fr_ntt_plan_create.restype = vp
+        L.ctt_hip_fr_ntt_plan_destroy.argtypes = [vp, vp]
+        L.ctt_hip_fr_ntt_plan_destroy.restype = None
+        L.ctt_hip_fr_ntt_plan_info.argtypes = [vp, vp]
+        L.ctt_hip_fr_ntt_plan_info.restype = i32
+        L.ctt_hip_fr_ntt.argtypes = [vp, vp, vp, vp, sz, i32, vp]
+        L.ctt_hip_fr_ntt.restype = i32
+    if "ctt_eth_kzg_compute_cells_and_kzg_proofs" not in missing:
+        L.ctt_eth_kzg_compute_cells_and_kzg_proofs.argtypes = [vp, vp, vp, vp]
+        L.ctt_eth_kzg_compute_cells_and_kzg_proofs.restype = ctypes.c_uint8
+        L.ctt_hip_eth_kzg_compute_cells.argtypes = [vp, vp, vp]
+        L.ctt_hip_eth_kzg_compute_cells.restype = ctypes.c_uint8
+        L.ctt_hip_eth_kzg_cell_quotients.argtypes = [vp, vp, vp]
+        L.ctt_hip_eth_kzg_cell_quotients.restype = ctypes.c_uint8
+        L.ctt_hip_eth_kzg_last_cell_timings.argtypes = [vp, vp, i32]
+        L.ctt_hip_eth_kzg_last_cell_timings.restype = i32
     _lib = L
     return L

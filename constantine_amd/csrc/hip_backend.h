@@ -6,6 +6,7 @@
 #include "generators.h"
 #include "hip_errors.h"
 #include "msm_pipeline.h"
+#include "ntt.h"
 
 namespace ctt {
 
@@ -988,6 +989,8 @@ struct CurveOps {
   // Returns 0, or -2 when z is one of the n-th roots of unity (the caller's other formula applies).
   int (*fr_quotient)(HipBackend* bk, const void* d_poly, const void* d_dom, const void* z_host, uint32_t n, void* d_work,
                      void* d_q, void* y_host);
+  // the batched NTT over the curve's scalar field: the table of C::Fr, shared by the curves with the same one (ntt.h)
+  const NttOps* ntt;
   // --- host only
   // r_aff = sum of n affine points (combining the per-GPU partial results of a sharded MSM,
   // the `r ~+= partial` of ec_multi_scalar_mul_parallel.nim:427-429)
@@ -1200,6 +1203,7 @@ struct CurveImpl {
       t.batch_affine = batch_affine;
       t.subgroup_check = subgroup_check;
       t.fr_quotient = fr_quotient;
+      t.ntt = ntt_ops_for<typename C::Fr::Params>();
       t.ec_sum_affine = ec_sum_affine;
       t.subgroup_check_host = subgroup_check_host;
       return t;

@@ -9,7 +9,13 @@
 // Host side in C++: wire formats, range / curve checks, the Fiat-Shamir hash, point (de)compression.  GPU side: every MSM
 // (cached SRS: ctt_hip_msm_with_bases; precompile inputs: ctt_hip_msm_host), the subgroup checks (ctt_hip_subgroup_check) and
 // the quotient polynomial of an opening (ctt_hip_fr_quotient; the branch "z is a root of unity" runs the reference's other
-// formula here on the host).  Verification needs pairings and is out of scope, like the PeerDAS cell functions.
+// formula here on the host).  Verification needs pairings and is out of scope.
+//
+//   EIP-7594 PeerDAS ctt_eth_kzg_compute_cells_and_kzg_proofs (include/constantine/protocols/ethereum_eip7594_peerdas.h) and the
+//                   cells alone (ctt_hip_eth_kzg_compute_cells): the blob's coefficients, the coset evaluations and the 128 cell
+//                   quotients' evaluations are transforms of ctt_hip_fr_ntt (ntt.hip), the quotients one kernel here
+//                   (k_cell_quotients), the proofs 128 MSMs over the context's cached Lagrange bases.  Recovery, the batch
+//                   verification (pairings) and the FK20 form are out of scope.  DESIGN.md section 13.
 #include <hip/hip_runtime.h>
 #include <ctype.h>
 #include <stdio.h>
@@ -30,6 +36,7 @@
 #include "host_fp64.h"
 #include "hip_errors.h"
 #include "msm_pipeline.h"   // (OutOfDeviceMemory)
+#include "ntt_bodies.h"
 
 // (part 3 of the header declares this file's symbols with the reference's packed enums and byte-array structs; the definitions
 // below spell the same ABI with uint8_t and plain pointers, so the typed declarations stay out of this translation unit)
@@ -489,9 +496,57 @@ struct ctt_eth_kzg_context_struct {
   void* d_domain = nullptr;     // the same on the device (ctt_hip_fr_quotient's layout)
   void* d_poly = nullptr;       // 4096 canonical scalars of the blob being opened
   void* d_q = nullptr;          // quotient evaluations (never leave the GPU before the MSM)
+  // EIP-7594: one plan of size 4096 serves the inverse transform of the blob, the coset transform of the cells and the batched one
+  // of the cell quotients (a plan of ctt_hip_fr_ntt runs both directions); c_k of the 128 cells; the blob's coefficients (Montgomery)
+  // and coset evaluations; the 128 x 4096 quotient coefficients / evaluations (16 MiB, allocated at the first proof call)
+  ctt_hip_ntt_plan* ntt = nullptr;
+  void* d_ck = nullptr;
+  void* d_coef = nullptr;
+  void* d_coset = nullptr;
+  void* d_cellq = nullptr;
+  uint8_t coset_shift[32];      // omega_8192, canonical
+  float cell_ms[7] = {0, 0, 0, 0, 0, 0, 0};   // the last cells call: parse + upload, INTT, coset NTT, quotients, batched NTT, MSM loop, compress + copy back
 };
 
 namespace {
+
+// ---- EIP-7594 cells and cell proofs ---------------------------------------------------------------------------------------------
+constexpr int N_CELLS = 128, CELL_ELEMS = 64, CELL_BYTES = CELL_ELEMS * 32;
+using FrD = Fp<BLS12_381_Fr>;
+
+// The quotients of the blob's polynomial p by X^64 - c_k, k < 128, in coefficient form: q_k[j] = p[j + 64] + c_k * q_k[j + 64] with
+// q_k[j] = 0 from j = 4032 on -- a Horner walk with stride 64, so lane (k, s) owns the residue class s mod 64 of cell k and walks it
+// downwards: 63 multiply-adds.  The 64 lanes of a cell read and write neighbouring elements.  The remainder (the cell's interpolant)
+// is never needed.  p, c_k Montgomery; q Montgomery, or canonical with `canon` (the test-facing ctt_hip_eth_kzg_cell_quotients).
+struct CellQuotArgs {
+  const uint32_t* p;    // [4096]
+  const uint32_t* ck;   // [128]
+  uint32_t* q;          // [128][4096]
+  uint32_t canon;
+};
+CTT_HD void cell_quotient_body(const CellQuotArgs& a, uint32_t lane) {
+  if (lane >= (uint32_t)(N_CELLS * CELL_ELEMS)) return;
+  const uint32_t k = lane / CELL_ELEMS, s = lane % CELL_ELEMS;
+  const FrD c = ntt_ld<FrD>(a.ck, k);
+  const uint64_t row = (uint64_t)k * N_BLOB;
+  FrD acc = FrD::zero();
+  ntt_st<FrD>(a.q, row + s + 64u * 63u, acc);
+  for (int m = 62; m >= 0; m--) {
+    acc = FrD::add(ntt_ld<FrD>(a.p, s + 64u * (uint32_t)(m + 1)), FrD::mul(c, acc));
+    ntt_st<FrD>(a.q, row + s + 64u * (uint32_t)m, a.canon ? FrD::from_mont(acc) : acc);
+  }
+}
+__global__ void __launch_bounds__(256) k_cell_quotients(CellQuotArgs a) { cell_quotient_body(a, blockIdx.x * blockDim.x + threadIdx.x); }
+
+// 7^((r-1)/2^log2n), Montgomery
+FrH root_of_unity(int log2n) {
+  uint64_t e[4];
+  for (int i = 0; i < 4; i++) e[i] = FrH::P(i);
+  e[0] -= 1;
+  for (int i = 0; i < 4; i++) e[i] = (e[i] >> log2n) | (i + 1 < 4 ? e[i + 1] << (64 - log2n) : 0);
+  const uint64_t seven[4] = {7, 0, 0, 0};
+  return fpow<FrH>(to_mont<FrH>(seven), e, 4);
+}
 
 // srs: 4096 x 48 compressed G1 Lagrange points in ceremony (file) order
 int kzg_context_build(ctt_eth_kzg_context_struct** out, const uint8_t* srs, int device, int table) {
@@ -515,6 +570,11 @@ int kzg_context_build(ctt_eth_kzg_context_struct** out, const uint8_t* srs, int 
     if (c->d_domain) (void)hipFree(c->d_domain);
     if (c->d_poly) (void)hipFree(c->d_poly);
     if (c->d_q) (void)hipFree(c->d_q);
+    if (c->d_ck) (void)hipFree(c->d_ck);
+    if (c->d_coef) (void)hipFree(c->d_coef);
+    if (c->d_coset) (void)hipFree(c->d_coset);
+    if (c->d_cellq) (void)hipFree(c->d_cellq);
+    if (c->ntt) ctt_hip_fr_ntt_plan_destroy(c->hip, c->ntt);
     if (c->hip) ctt_hip_msm_ctx_destroy(c->hip);
     delete c;
     return st;
@@ -536,8 +596,28 @@ int kzg_context_build(ctt_eth_kzg_context_struct** out, const uint8_t* srs, int 
     PROT_HIP_CHECK(hipMalloc(&c->d_poly, (size_t)N_BLOB * 32));
     PROT_HIP_CHECK(hipMalloc(&c->d_q, (size_t)N_BLOB * 32));
     PROT_HIP_CHECK(hipMemcpy(c->d_domain, c->domain.data(), (size_t)N_BLOB * 32, hipMemcpyHostToDevice));
+    // EIP-7594: c_k = omega_8192^(64 * brp7(k)), the coset of cell k is c_k^(1/64) * <omega_64>
+    const FrH w8192 = root_of_unity(13);
+    std::vector<FrH> ck(N_CELLS);
+    for (int k = 0; k < N_CELLS; k++) {
+      const uint64_t e[1] = {64ull * bit_reverse((uint32_t)k, 7)};
+      ck[k] = e[0] ? fpow<FrH>(w8192, e, 1) : FrH::one();
+    }
+    uint64_t g[4];
+    from_mont<FrH>(w8192, g);
+    memcpy(c->coset_shift, g, 32);
+    PROT_HIP_CHECK(hipMalloc(&c->d_ck, (size_t)N_CELLS * 32));
+    PROT_HIP_CHECK(hipMalloc(&c->d_coef, (size_t)N_BLOB * 32));
+    PROT_HIP_CHECK(hipMalloc(&c->d_coset, (size_t)N_BLOB * 32));
+    PROT_HIP_CHECK(hipMemcpy(c->d_ck, ck.data(), (size_t)N_CELLS * 32, hipMemcpyHostToDevice));
   } catch (const HipFailure&) {
     return fail(GPU_UNAVAILABLE);
+  }
+  {
+    uint64_t w[4];
+    from_mont<FrH>(root_of_unity(12), w);
+    c->ntt = ctt_hip_fr_ntt_plan_create(c->hip, CTT_HIP_BLS12_381_G1, 12, w, 0);
+    if (!c->ntt) return fail(GPU_UNAVAILABLE);
   }
   *out = c;
   return TS_Success;
@@ -567,6 +647,104 @@ int kzg_prove(ctt_eth_kzg_context_struct* c, uint8_t proof[48], uint64_t y_c[4],
   if (mrc != 0) return GPU_UNAVAILABLE;
   memcpy(y_c, y_tmp, 32);
   g1_compress(proof, r_aff);
+  return KZG_Success;
+}
+
+// EIP-7594 compute_cells / compute_cells_and_kzg_proofs (ethereum_eip7594_peerdas.h; the formulas: DESIGN.md section 13) for a
+// validated polynomial.  cells: 128 x 2048 bytes or NULL; proofs: 128 x 48 bytes or NULL; q_le: 128 x 4096 canonical quotient
+// coefficients or NULL (the probe of the quotient kernel; nothing else is computed then).  Outputs are written at the very end only.
+int kzg_cells(ctt_eth_kzg_context_struct* c, uint8_t* cells, uint8_t* proofs, uint8_t* q_le, const uint8_t* blob, const uint8_t* poly_le, float parse_ms) {
+  using clk = std::chrono::steady_clock;
+  auto ms_since = [](clk::time_point& t0) {
+    const clk::time_point t1 = clk::now();
+    const float ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
+    t0 = t1;
+    return ms;
+  };
+  std::lock_guard<std::mutex> lock(c->mu);
+  DeviceScope device_scope(c->device);
+  hipStream_t s = (hipStream_t)ctt_hip_msm_stream(c->hip);
+  if (!s) return GPU_UNAVAILABLE;
+  float ms[7] = {0, 0, 0, 0, 0, 0, 0};
+  clk::time_point t0 = clk::now();
+  PROT_HIP_CHECK(hipMemcpyAsync(c->d_poly, poly_le, (size_t)N_BLOB * 32, hipMemcpyHostToDevice, s));
+  PROT_HIP_CHECK(hipStreamSynchronize(s));
+  ms[0] = parse_ms + ms_since(t0);
+  // 1. coefficients: the blob holds evaluations in bit-reversed order
+  if (ctt_hip_fr_ntt(c->hip, c->ntt, c->d_coef, c->d_poly, 1, CTT_HIP_NTT_INVERSE | CTT_HIP_NTT_IN_BRP | CTT_HIP_NTT_OUT_MONT, nullptr) != 0)
+    return GPU_UNAVAILABLE;
+  ms[1] = ms_since(t0);
+  std::vector<uint8_t> coset;
+  if (cells) {
+    // 2. the second half of the extended evaluations: the coset omega_8192 * <omega_4096>, bit-reversed, canonical
+    if (ctt_hip_fr_ntt(c->hip, c->ntt, c->d_coset, c->d_coef, 1, CTT_HIP_NTT_IN_MONT | CTT_HIP_NTT_OUT_BRP, c->coset_shift) != 0)
+      return GPU_UNAVAILABLE;
+    coset.resize((size_t)N_BLOB * 32);
+    PROT_HIP_CHECK(hipMemcpyAsync(coset.data(), c->d_coset, coset.size(), hipMemcpyDeviceToHost, s));
+    PROT_HIP_CHECK(hipStreamSynchronize(s));
+    ms[2] = ms_since(t0);
+  }
+  std::vector<uint8_t> aff;
+  std::vector<uint8_t> q_host;
+  if (proofs || q_le) {
+    if (!c->d_cellq) {
+      const hipError_t e = hipMalloc(&c->d_cellq, (size_t)N_CELLS * N_BLOB * 32);
+      if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        c->d_cellq = nullptr;
+        throw OutOfDeviceMemory{(size_t)N_CELLS * N_BLOB * 32};
+      }
+      PROT_HIP_CHECK(e);
+    }
+    // 3. the 128 quotients by X^64 - c_k
+    CellQuotArgs qa{(const uint32_t*)c->d_coef, (const uint32_t*)c->d_ck, (uint32_t*)c->d_cellq, q_le ? 1u : 0u};
+    hipLaunchKernelGGL(k_cell_quotients, dim3(N_CELLS * CELL_ELEMS / 256), dim3(256), 0, s, qa);
+    PROT_HIP_CHECK(hipGetLastError());
+    if (q_le) {
+      q_host.resize((size_t)N_CELLS * N_BLOB * 32);
+      PROT_HIP_CHECK(hipMemcpyAsync(q_host.data(), c->d_cellq, q_host.size(), hipMemcpyDeviceToHost, s));
+    }
+    PROT_HIP_CHECK(hipStreamSynchronize(s));
+    ms[3] = ms_since(t0);
+  }
+  if (proofs) {
+    // 4. their evaluations over the domain of the Lagrange bases (bit-reversed, canonical: the MSM's coefficients), in place
+    if (ctt_hip_fr_ntt(c->hip, c->ntt, c->d_cellq, c->d_cellq, N_CELLS, CTT_HIP_NTT_IN_MONT | CTT_HIP_NTT_OUT_BRP, nullptr) != 0) return GPU_UNAVAILABLE;
+    ms[4] = ms_since(t0);
+    // 5. 128 MSMs over the cached bases, three tickets in flight (the header's advice for small MSMs)
+    aff.resize((size_t)N_CELLS * 96);
+    int ticket[N_CELLS];
+    int submitted = 0, finished = 0;
+    bool failed = false;
+    while (!failed && finished < N_CELLS) {
+      if (submitted < N_CELLS && submitted - finished < 3) {
+        ticket[submitted] = ctt_hip_msm_with_bases_submit(c->hip, c->bases, CTT_HIP_COEF_BIG, (const uint8_t*)c->d_cellq + (size_t)submitted * N_BLOB * 32, N_BLOB);
+        if (ticket[submitted] < 0) failed = true;
+        else submitted++;
+      } else {
+        if (ctt_hip_msm_device_finish(c->hip, ticket[finished], CTT_HIP_OUT_AFF, aff.data() + (size_t)finished * 96) != 0) failed = true;
+        finished++;
+      }
+    }
+    if (failed) {   // give the outstanding tickets back: their slots would stay taken on this context
+      uint8_t dummy[96];
+      for (; finished < submitted; finished++) (void)ctt_hip_msm_device_finish(c->hip, ticket[finished], CTT_HIP_OUT_AFF, dummy);
+      return GPU_UNAVAILABLE;
+    }
+    ms[5] = ms_since(t0);
+  }
+  // 6. the outputs: the first half of the cells is the blob itself, the second the coset evaluations as big-endian bytes
+  if (cells) {
+    memcpy(cells, blob, (size_t)N_BLOB * 32);
+    uint8_t* second = cells + (size_t)N_BLOB * 32;
+    for (int i = 0; i < N_BLOB; i++)
+      for (int b = 0; b < 32; b++) second[32 * i + b] = coset[32 * i + 31 - b];
+  }
+  if (proofs)
+    for (int k = 0; k < N_CELLS; k++) g1_compress(proofs + 48 * k, aff.data() + (size_t)k * 96);
+  if (q_le) memcpy(q_le, q_host.data(), q_host.size());
+  ms[6] = ms_since(t0);
+  memcpy(c->cell_ms, ms, sizeof ms);
   return KZG_Success;
 }
 
@@ -615,9 +793,10 @@ int ctt_hip_eth_kzg_context_from_srs(ctt_eth_kzg_context_struct** ctx, const uin
 // The reader follows load_ckzg4844 (constantine/commitments_setups/ethereum_kzg_srs.nim:242-350): "%4u" counts, then 4096 Lagrange
 // G1 lines of exactly 96 hex characters, 65 monomial G2 lines of exactly 192, 4096 monomial G1 lines of 96, LF or CRLF line ends;
 // anything else -- a short file, a long line, a character that is not a hex digit -- is cttEthTS_InvalidFile.  The Lagrange points
-// are decompressed and subgroup-checked (they are the commitment key).  The G2 and monomial-G1 sections serve verification and
-// the PeerDAS proofs, which are out of scope here: their lines are checked for length, hex digits, the compression flag and
-// coordinates below p, not decompressed (round 4 did not read them at all: a truncated file loaded -- ADVICE r4).
+// are decompressed and subgroup-checked (they are the commitment key, and the key of the EIP-7594 cell proofs).  The G2 and
+// monomial-G1 sections serve verification and the FK20 form of the cell proofs, neither of which this library has: their lines are
+// checked for length, hex digits, the compression flag and coordinates below p, not decompressed (round 4 did not read them at all:
+// a truncated file loaded -- ADVICE r4).
 static bool srs_hex_line(FILE* f, size_t hex_chars, uint8_t* out) {
   char buf[200];
   size_t got = 0;
@@ -680,7 +859,7 @@ uint8_t ctt_eth_kzg_context_new(ctt_eth_kzg_context_struct** ctx, const char* fi
 }
 // ethereum_eip4844_kzg.h:232: the reference's constructor with PrecomputedMSM lookup tables (t base groups, b bits per window -- CPU
 // tables for the FK20 proofs of PeerDAS).  The same context as above: the SRS is cached on the GPU as a window table whatever t and b
-// say; the PeerDAS functions those tables serve are not part of this library.
+// say; the cell proofs here are MSMs over that table, not FK20.
 uint8_t ctt_eth_kzg_context_new_with_precompute(ctt_eth_kzg_context_struct** ctx, const char* filepath, uint8_t format, int /*t*/, int /*b*/) {
   return ctt_eth_kzg_context_new(ctx, filepath, format);
 }
@@ -694,6 +873,11 @@ void ctt_eth_kzg_context_delete(ctt_eth_kzg_context_struct* c) {
     if (c->d_domain) (void)hipFree(c->d_domain);
     if (c->d_poly) (void)hipFree(c->d_poly);
     if (c->d_q) (void)hipFree(c->d_q);
+    if (c->d_ck) (void)hipFree(c->d_ck);
+    if (c->d_coef) (void)hipFree(c->d_coef);
+    if (c->d_coset) (void)hipFree(c->d_coset);
+    if (c->d_cellq) (void)hipFree(c->d_cellq);
+    if (c->ntt) ctt_hip_fr_ntt_plan_destroy(c->hip, c->ntt);
     if (c->own_hip) ctt_hip_msm_ctx_destroy(c->hip);
     return 0;
   });
@@ -750,6 +934,38 @@ uint8_t ctt_eth_kzg_compute_blob_kzg_proof(const ctt_eth_kzg_context_struct* ctx
   uint64_t z[4], y[4];
   fiat_shamir_challenge(z, blob, commitment);
   return gpu_guarded([&]() { return kzg_prove(c, proof, y, poly.data(), z); });
+}
+
+// ---- EIP-7594 (ethereum_eip7594_peerdas.h: compute_cells_and_kzg_proofs; the cells alone are the Nim API's compute_cells) --------
+// cells: 128 x ctt_eth_kzg_cell {byte raw[2048]}; proofs: 128 x 48 bytes.  Nothing is written on any status but Success.
+static uint8_t cells_entry(const ctt_eth_kzg_context_struct* ctx, uint8_t* cells, uint8_t* proofs, uint8_t* q_le, const uint8_t* blob) {
+  ctt_eth_kzg_context_struct* c = const_cast<ctt_eth_kzg_context_struct*>(ctx);
+  std::vector<uint8_t> poly((size_t)N_BLOB * 32);
+  const auto t0 = std::chrono::steady_clock::now();
+  const int st = blob_to_scalars(poly.data(), blob);
+  if (st != KZG_Success) return (uint8_t)st;
+  const float parse_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return gpu_guarded([&]() { return kzg_cells(c, cells, proofs, q_le, blob, poly.data(), parse_ms); });
+}
+uint8_t ctt_eth_kzg_compute_cells_and_kzg_proofs(const ctt_eth_kzg_context_struct* ctx, uint8_t* cells, uint8_t* proofs, const uint8_t* blob) {
+  return cells_entry(ctx, cells, proofs, nullptr, blob);
+}
+uint8_t ctt_hip_eth_kzg_compute_cells(const ctt_eth_kzg_context_struct* ctx, uint8_t* cells, const uint8_t* blob) {
+  return cells_entry(ctx, cells, nullptr, nullptr, blob);
+}
+// test-facing: the 128 x 4096 canonical little-endian coefficients q_k[j] of the cell quotients (k_cell_quotients alone)
+uint8_t ctt_hip_eth_kzg_cell_quotients(const ctt_eth_kzg_context_struct* ctx, uint8_t* q_le, const uint8_t* blob) {
+  return cells_entry(ctx, nullptr, nullptr, q_le, blob);
+}
+// host-clock times (ms) of the context's last cells call, every step waited for: parse + upload, INTT, coset NTT, quotients,
+// batched NTT, MSM loop, compress + copy back.  Returns the number written.
+int ctt_hip_eth_kzg_last_cell_timings(const ctt_eth_kzg_context_struct* ctx, float* ms, int cap) {
+  if (!ctx || !ms) return -1;
+  ctt_eth_kzg_context_struct* c = const_cast<ctt_eth_kzg_context_struct*>(ctx);
+  std::lock_guard<std::mutex> lock(c->mu);
+  const int n = cap < 7 ? cap : 7;
+  for (int i = 0; i < n; i++) ms[i] = c->cell_ms[i];
+  return n;
 }
 
 // the _parallel forms (ethereum_eip4844_kzg_parallel.h:40,61,73): the thread pool is not used, as in the MSM's _parallel symbols

@@ -11,7 +11,16 @@ constantine_amd/csrc/protocols.hip):
 Wire parsing, range checks, the Fiat-Shamir hash and point (de)compression are C++ on the host, every MSM, the subgroup check
 and the quotient polynomial run on the GPU.  Nothing is computed in Python here; the only checks this module adds are the byte
 LENGTHS, which the C signatures fix by type (ctt_eth_kzg_blob = 131072 bytes ...) and a Python `bytes` does not.  Verification
-needs pairings and is out of scope, like the cell / PeerDAS functions.
+needs pairings and is out of scope.
+
+EIP-7594 (PeerDAS) on the same context:
+
+    ctt_eth_kzg_compute_cells_and_kzg_proofs   include/constantine/protocols/ethereum_eip7594_peerdas.h
+    ctt_hip_eth_kzg_compute_cells              the cells alone (the reference's Nim API has it, its C header does not)
+
+The blob's coefficients, the coset evaluations of the cells and the evaluations of the 128 cell quotients are transforms of the
+scalar-field NTT (ntt.py); the proofs are 128 MSMs over the cached Lagrange SRS.  recover_cells_and_kzg_proofs,
+verify_cell_kzg_proof_batch (pairings) and the FK20 form of the proofs are out of scope.
 """
 import ctypes
 from enum import Enum
@@ -24,6 +33,8 @@ FIELD_ELEMENTS_PER_BLOB = 4096
 BYTES_PER_FIELD_ELEMENT = 32
 BYTES_PER_BLOB = FIELD_ELEMENTS_PER_BLOB * BYTES_PER_FIELD_ELEMENT
 BYTES_PER_COMMITMENT = 48
+CELLS_PER_EXT_BLOB = 128
+BYTES_PER_CELL = 2048
 
 
 class cttEthKzgStatus(Enum):  # ethereum_eip4844_kzg.h:29-40
@@ -130,6 +141,44 @@ def compute_blob_kzg_proof(ctx: EthereumKZGContext, blob: bytes, commitment_byte
     proof = (ctypes.c_uint8 * 48)()
     _check(ctx.L.ctt_eth_kzg_compute_blob_kzg_proof(ctx.handle, proof, _buf(blob), _buf(commitment_bytes)))
     return bytes(proof)
+
+
+def compute_cells(ctx: EthereumKZGContext, blob: bytes):
+    """-> the 128 cells of the extended blob, 2048 bytes each (ctt_hip_eth_kzg_compute_cells)"""
+    if len(blob) != BYTES_PER_BLOB:
+        raise KzgError(cttEthKzgStatus.cttEthKzg_InputsLengthsMismatch)
+    cells = (ctypes.c_uint8 * (CELLS_PER_EXT_BLOB * BYTES_PER_CELL))()
+    _check(ctx.L.ctt_hip_eth_kzg_compute_cells(ctx.handle, cells, _buf(blob)))
+    raw = bytes(cells)
+    return [raw[BYTES_PER_CELL * k:BYTES_PER_CELL * (k + 1)] for k in range(CELLS_PER_EXT_BLOB)]
+
+
+def compute_cells_and_kzg_proofs(ctx: EthereumKZGContext, blob: bytes):
+    """-> (128 cells of 2048 bytes, 128 proofs of 48 bytes): ctt_eth_kzg_compute_cells_and_kzg_proofs"""
+    if len(blob) != BYTES_PER_BLOB:
+        raise KzgError(cttEthKzgStatus.cttEthKzg_InputsLengthsMismatch)
+    cells = (ctypes.c_uint8 * (CELLS_PER_EXT_BLOB * BYTES_PER_CELL))()
+    proofs = (ctypes.c_uint8 * (CELLS_PER_EXT_BLOB * 48))()
+    _check(ctx.L.ctt_eth_kzg_compute_cells_and_kzg_proofs(ctx.handle, cells, proofs, _buf(blob)))
+    raw, pr = bytes(cells), bytes(proofs)
+    return ([raw[BYTES_PER_CELL * k:BYTES_PER_CELL * (k + 1)] for k in range(CELLS_PER_EXT_BLOB)],
+            [pr[48 * k:48 * (k + 1)] for k in range(CELLS_PER_EXT_BLOB)])
+
+
+def cell_quotients(ctx: EthereumKZGContext, blob: bytes) -> np.ndarray:
+    """ctt_hip_eth_kzg_cell_quotients (test-facing): the coefficients q_k[j] of p / (X^64 - c_k), (128, 4096, 32) uint8 little-endian"""
+    if len(blob) != BYTES_PER_BLOB:
+        raise KzgError(cttEthKzgStatus.cttEthKzg_InputsLengthsMismatch)
+    q = np.zeros((CELLS_PER_EXT_BLOB, FIELD_ELEMENTS_PER_BLOB, 32), dtype=np.uint8)
+    _check(ctx.L.ctt_hip_eth_kzg_cell_quotients(ctx.handle, q.ctypes.data_as(ctypes.c_void_p), _buf(blob)))
+    return q
+
+
+def last_cell_timings(ctx: EthereumKZGContext):
+    """host-clock ms of the context's last cells call: parse + upload, INTT, coset NTT, quotients, batched NTT, MSM loop, compress + copy back"""
+    ms = (ctypes.c_float * 7)()
+    ctx.L.ctt_hip_eth_kzg_last_cell_timings(ctx.handle, ms, 7)
+    return list(ms)
 
 
 # the reference's _parallel forms (ethereum_eip4844_kzg_parallel.nim: `tp` first): the same GPU path, the thread pool is not used

@@ -350,8 +350,10 @@ void* ctt_hip_msm_stream(ctt_hip_msm_ctx* ctx);
  *       :153 (compute_blob_kzg_proof), :200 (context_new), :238 (context_delete)
  *   include/constantine/protocols/ethereum_evm_precompiles.h:386 (g1msm), :419 (g2msm)
  * (constantine/ethereum_eip4844_kzg.nim:297-444, constantine/ethereum_evm_precompiles.nim:894-1060).  Host side in C++
- * (constantine_amd/csrc/protocols.hip), MSMs / subgroup checks / quotient polynomial on the GPU.  Verification (pairings), the
- * PeerDAS cell functions and the other precompiles are out of scope and not exported.  There is no CPU fallback, and none of
+ * (constantine_amd/csrc/protocols.hip), MSMs / subgroup checks / quotient polynomial on the GPU.  Verification (pairings) and the
+ * other precompiles are out of scope and not exported.  EIP-7594 (PeerDAS): compute_cells_and_kzg_proofs of
+ *   include/constantine/protocols/ethereum_eip7594_peerdas.h
+ * and the cells alone; recover_cells_and_kzg_proofs, verify_cell_kzg_proof_batch and the FK20 form are out of scope.  There is no CPU fallback, and none of
  * these symbols terminates the process (round 5; rounds 1-4 aborted): a call the GPU cannot serve -- no device, out of device
  * memory, a failed HIP call -- returns CTT_HIP_STATUS_GPU_UNAVAILABLE, a value outside every status enum below (the reference's
  * *_status_to_string print "InvalidStatusCode" for it), leaves its outputs untouched, and ctt_hip_last_error() of the calling
@@ -402,6 +404,20 @@ ctt_eth_kzg_status ctt_eth_kzg_compute_kzg_proof_parallel(const ctt_threadpool* 
 ctt_eth_kzg_status ctt_eth_kzg_compute_blob_kzg_proof_parallel(const ctt_threadpool* tp, const ctt_eth_kzg_context* ctx,
                                                                ctt_eth_kzg_proof* proof, const ctt_eth_kzg_blob* blob,
                                                                const ctt_eth_kzg_commitment* commitment);
+/* EIP-7594: cells[128] and proofs[128] of the extended blob.  The cells' second half is the coset transform of the blob's
+ * coefficients, proof k the MSM of the evaluations of p / (X^64 - c_k) over the context's cached Lagrange SRS (Part 5's NTT; 16 MiB
+ * of device memory from the first call on).  Nothing is written on any status but Success.  The context is not modified as the
+ * caller sees it (it serialises its calls). */
+typedef struct { ctt_byte raw[2048]; }      ctt_eth_kzg_cell;
+ctt_eth_kzg_status ctt_eth_kzg_compute_cells_and_kzg_proofs(const ctt_eth_kzg_context* ctx, ctt_eth_kzg_cell cells[128],
+                                                            ctt_eth_kzg_proof proofs[128], const ctt_eth_kzg_blob* blob);
+/* not in the reference's C header (its Nim API has compute_cells): the cells alone -- two transforms, no MSM */
+ctt_eth_kzg_status ctt_hip_eth_kzg_compute_cells(const ctt_eth_kzg_context* ctx, ctt_eth_kzg_cell cells[128], const ctt_eth_kzg_blob* blob);
+/* test-facing: the 128 x 4096 canonical little-endian coefficients of the cell quotients (the quotient kernel alone), and the
+ * host-clock times (ms) of the context's last cells call: parse + upload, INTT, coset NTT, quotients, batched NTT, MSM loop,
+ * compress + copy back (returns the number written) */
+ctt_eth_kzg_status ctt_hip_eth_kzg_cell_quotients(const ctt_eth_kzg_context* ctx, uint8_t* q_le, const ctt_eth_kzg_blob* blob);
+int ctt_hip_eth_kzg_last_cell_timings(const ctt_eth_kzg_context* ctx, float* ms, int cap);
 ctt_evm_status ctt_eth_evm_bls12381_g1msm(ctt_byte* r, size_t r_len, const ctt_byte* inputs, size_t inputs_len);
 ctt_evm_status ctt_eth_evm_bls12381_g2msm(ctt_byte* r, size_t r_len, const ctt_byte* inputs, size_t inputs_len);
 
@@ -465,6 +481,37 @@ int ctt_hip_verkle_update_batch(ctt_hip_msm_ctx* ctx, const ctt_hip_verkle_crs* 
 /* HIP-event times (ms) of the context's last commit or update batch -- recorded while the option "timings" is non-zero -- and of its
  * last table build: commit (update) kernel, finish kernel(s), table build.  Returns 0, or -1 without a usable context. */
 int ctt_hip_verkle_last_timings(ctt_hip_msm_ctx* ctx, float* ms, int cap);
+
+/* ---- Part 5: batched number-theoretic transform over a curve's scalar field -------------------------------------------------
+ * n = 2^log2n elements of 32 bytes per row, log2n from 1 to min(24, the two-adicity of the field: 32 for BLS12-381, Pallas and
+ * Vesta, 28 for BN254-Snarks, 5 for Banderwagon); G1 and G2 of a pairing curve share their field.  A plan holds the table
+ * omega^i, i < n/2 (16 * n bytes of device memory) on its context; destroy it before the context.
+ *   plan_create  omega: 32 canonical little-endian bytes on the host, checked there: below the modulus and omega^(n/2) == -1.
+ *                tile_log2: radix-2 stages per pass, 1 .. 9, 0 = the default (8).  NULL on refusal (last error -1, -2 or -3).
+ *   fr_ntt       d_in, d_out: device memory, 16-byte aligned, `batch` rows of n elements; d_out may equal d_in (rows may not
+ *                overlap otherwise).  shift: NULL, or a non-zero canonical scalar g on the host (the coset g * <omega>).
+ *                  forward   out[k] = sum_i (g^i * in[i]) * omega^(i*k)
+ *                  inverse   out[i] = g^(-i) * n^(-1) * sum_k in[k] * omega^(-i*k)          (CTT_HIP_NTT_INVERSE)
+ *                i and k are natural indices; CTT_HIP_NTT_IN_BRP / _OUT_BRP say that a side is laid out in bit-reversed order
+ *                (element i at position brp(i)).  With _IN_MONT / _OUT_MONT that side holds Montgomery residues, else canonical
+ *                little-endian scalars -- the MSM's CTT_HIP_COEF_BIG -- fully reduced on output; the conversion is part of the
+ *                first load and the last store.  batch * n <= 2^26; batch == 0 returns 0 and touches nothing.
+ * Blocking, on the context's main stream: ordered against the MSM submits of the same context.  Returns 0; -1 refused before any
+ * launch (a NULL pointer, misaligned pointers, unknown flag bits, a shift of zero or >= the modulus, a plan of another context,
+ * batch * n too large); -2 out of device memory (the n multipliers of a shift, kept with the plan).  ctx == NULL is the default
+ * context. */
+#define CTT_HIP_NTT_INVERSE 1
+#define CTT_HIP_NTT_IN_BRP 2
+#define CTT_HIP_NTT_OUT_BRP 4
+#define CTT_HIP_NTT_IN_MONT 8
+#define CTT_HIP_NTT_OUT_MONT 16
+typedef struct ctt_hip_ntt_plan ctt_hip_ntt_plan;
+ctt_hip_ntt_plan* ctt_hip_fr_ntt_plan_create(ctt_hip_msm_ctx* ctx, int curve, int log2n, const void* omega, int tile_log2);
+void ctt_hip_fr_ntt_plan_destroy(ctt_hip_msm_ctx* ctx, ctt_hip_ntt_plan* plan);
+int ctt_hip_fr_ntt(ctt_hip_msm_ctx* ctx, const ctt_hip_ntt_plan* plan, void* d_out, const void* d_in, size_t batch, int flags,
+                   const void* shift);
+/* info[0..3] = log2n, tile_log2, passes of a natural-order-in transform, bytes of the twiddle table; 0, or -1 for a NULL */
+int ctt_hip_fr_ntt_plan_info(const ctt_hip_ntt_plan* plan, size_t info[4]);
 
 #ifdef __cplusplus
 }
