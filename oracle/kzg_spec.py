@@ -1,7 +1,7 @@
 """
 Spec restatement of the EIP-4844 host logic in plain Python integers -- TEST INFRASTRUCTURE (like everything under oracle/):
-what the C++ host side of the protocol symbols (constantine_amd/csrc/protocols.hip) and the device quotient kernel are checked
-against.  Only tests/ import it.  Follows
+what the C++ host side of the protocol symbols (constantine_amd/csrc/protocols_host.h, included by protocols.hip and by
+tests/protocols_harness.cpp) and the device quotient kernel are checked against.  Only tests/ import it.  Follows
     constantine/ethereum_eip4844_kzg.nim:103-166 (fromDigest, fiatShamirChallenge, bytes_to_bls_field), :297-444
     constantine/commitments/kzg.nim:186-223 (kzg_commit, kzg_prove), math/polynomials/polynomials.nim (getQuotientPoly)
     constantine/serialization/codecs_bls12_381.nim (ZCash compressed G1)
