@@ -3,7 +3,8 @@ constantine_amd -- MI355X-native multi-scalar-multiplication engine behind Const
 
 Only what the MSM hot path needs lives here:
   csrc/     HIP kernels (gfx950) + the C ABI  (include/ctt_msm_hip.h)  -> libctt_msm_hip.so
-  _lib.py   ctypes loader (fails loudly if the HIP library is missing)
+  _lib.py   ctypes loader (fails loudly if the HIP library is missing) and the prototype tables of both libraries
+  _arrays.py  the pointer, result-buffer and stream-ordering helpers of every caller below
   msm.py    host-side mirror of the reference's entry points (multiScalarMul_vartime[_parallel],
             Halo2-ZAL CttEngine.msm) over the C ABI
   parallel.py  point-sharded multi-GPU MSM, one process per GPU (torch.distributed / RCCL); the in-library form, one

@@ -28,6 +28,7 @@ from enum import Enum
 import numpy as np
 
 from . import _lib
+from ._arrays import ptr
 
 FIELD_ELEMENTS_PER_BLOB = 4096
 BYTES_PER_FIELD_ELEMENT = 32
@@ -170,7 +171,7 @@ def cell_quotients(ctx: EthereumKZGContext, blob: bytes) -> np.ndarray:
     if len(blob) != BYTES_PER_BLOB:
         raise KzgError(cttEthKzgStatus.cttEthKzg_InputsLengthsMismatch)
     q = np.zeros((CELLS_PER_EXT_BLOB, FIELD_ELEMENTS_PER_BLOB, 32), dtype=np.uint8)
-    _check(ctx.L.ctt_hip_eth_kzg_cell_quotients(ctx.handle, q.ctypes.data_as(ctypes.c_void_p), _buf(blob)))
+    _check(ctx.L.ctt_hip_eth_kzg_cell_quotients(ctx.handle, ptr(q), _buf(blob)))
     return q
 
 
@@ -227,7 +228,7 @@ def blob_to_bigint_polynomial(blob: bytes) -> np.ndarray:
     if len(blob) != BYTES_PER_BLOB:
         raise KzgError(cttEthKzgStatus.cttEthKzg_InputsLengthsMismatch)
     out = np.zeros((FIELD_ELEMENTS_PER_BLOB, 32), dtype=np.uint8)
-    _check(_lib.lib().ctt_hip_eth_kzg_blob_to_scalars(out.ctypes.data_as(ctypes.c_void_p), _buf(blob)))
+    _check(_lib.lib().ctt_hip_eth_kzg_blob_to_scalars(ptr(out), _buf(blob)))
     return out
 
 
@@ -245,8 +246,7 @@ def quotient_polynomial_host(poly_le: np.ndarray, z: int):
     assert poly_le.shape == (FIELD_ELEMENTS_PER_BLOB, 32)
     q = np.zeros_like(poly_le)
     y = (ctypes.c_uint8 * 32)()
-    _lib.lib().ctt_hip_eth_kzg_quotient_host(q.ctypes.data_as(ctypes.c_void_p), y, poly_le.ctypes.data_as(ctypes.c_void_p),
-                                             _buf(z.to_bytes(32, "little")))
+    _lib.lib().ctt_hip_eth_kzg_quotient_host(ptr(q), y, ptr(poly_le), _buf(z.to_bytes(32, "little")))
     return q, int.from_bytes(bytes(y), "little")
 
 

@@ -18,6 +18,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from ._arrays import is_cuda, order, ptr, result_buffer
 from .curves import COEF_BIG, COEF_FR, CURVES, OUT_AFF, OUT_JAC, OUT_PRJ
 
 _COORD = {"jac": OUT_JAC, "prj": OUT_PRJ, "aff": OUT_AFF}
@@ -36,10 +37,6 @@ def _check(curve, coefs, points):
     return info, coefs, points
 
 
-def _ptr(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
-
-
 def _out_kind(info, coord):
     """CTT_HIP_OUT_* of `coord`; Banderwagon (twisted Edwards) has no Jacobian coordinates"""
     if coord not in _COORD or (coord == "jac" and info.cid == CURVES["banderwagon"].cid):
@@ -55,12 +52,12 @@ def multiScalarMul_vartime(curve, coefs, points, coord="jac", fr_coefs=False):
         _out_kind(info, coord)
         fn = getattr(_lib.banderwagon_lib(), f"ctt_banderwagon_ec_prj_multi_scalar_mul_{'fr' if fr_coefs else 'big'}_coefs_vartime")
         r = np.zeros(info.jac_bytes, dtype=np.uint8)
-        fn(_ptr(r), _ptr(coefs), _ptr(points), coefs.shape[0])
+        fn(ptr(r), ptr(coefs), ptr(points), coefs.shape[0])
         return r[:info.aff_bytes].copy() if coord == "aff" else r
     L = _lib.lib()
     fn = getattr(L, f"ctt_{info.sym}_{coord}_multi_scalar_mul_{'fr' if fr_coefs else 'big'}_coefs_vartime")
     r = np.zeros(info.jac_bytes, dtype=np.uint8)
-    fn(_ptr(r), _ptr(coefs), _ptr(points), coefs.shape[0])
+    fn(ptr(r), ptr(coefs), ptr(points), coefs.shape[0])
     return r
 
 
@@ -73,7 +70,7 @@ def multiScalarMul_vartime_parallel(tp, curve, coefs, points, coord="jac", fr_co
     L = _lib.lib()
     fn = getattr(L, f"ctt_{info.sym}_{coord}_multi_scalar_mul_{'fr' if fr_coefs else 'big'}_coefs_vartime_parallel")
     r = np.zeros(info.jac_bytes, dtype=np.uint8)
-    fn(ctypes.c_void_p(tp or 0), _ptr(r), _ptr(coefs), _ptr(points), coefs.shape[0])
+    fn(ptr(tp), ptr(r), ptr(coefs), ptr(points), coefs.shape[0])
     return r
 
 
@@ -97,12 +94,11 @@ def msm_host(curve, coefs, points, coord="jac", fr_coefs=False, typed=True):
     MsmRefused with the symbol's status instead of aborting."""
     info, coefs, points = _check(curve, coefs, points)
     L = _lib.lib()
-    nco = 2 if coord == "aff" else 3
-    r = np.zeros(nco * info.coord_bytes, dtype=np.uint8)
+    r = result_buffer(info, coord)
     if typed and coord != "aff":
-        rc = getattr(L, f"ctt_hip_msm_{info.sym}_{coord}_{'fr' if fr_coefs else 'big'}")(_ptr(r), _ptr(coefs), _ptr(points), coefs.shape[0])
+        rc = getattr(L, f"ctt_hip_msm_{info.sym}_{coord}_{'fr' if fr_coefs else 'big'}")(ptr(r), ptr(coefs), ptr(points), coefs.shape[0])
     else:
-        rc = L.ctt_hip_msm_host(info.cid, COEF_FR if fr_coefs else COEF_BIG, _COORD[coord], _ptr(r), _ptr(coefs), _ptr(points),
+        rc = L.ctt_hip_msm_host(info.cid, COEF_FR if fr_coefs else COEF_BIG, _COORD[coord], ptr(r), ptr(coefs), ptr(points),
                                 coefs.shape[0])
     if rc != 0:
         raise MsmRefused(rc)
@@ -133,40 +129,17 @@ class DeviceMsm:
         if self.L.ctt_hip_msm_set_option(self.ctx, key.encode(), int(value)) != 0:
             raise KeyError(key)
 
-    @staticmethod
-    def _dptr(t):
-        return ctypes.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
-
-    def _order(self, *tensors):
-        """Order the engine's stream after torch's current stream when an argument is a torch CUDA tensor: the engine
-        runs on its own non-blocking streams, so without this a kernel that is still producing the tensor could be
-        overtaken (ctt_hip_msm_wait_stream; INTEGRATION.md "Stream ordering").  Raw integer addresses carry no stream:
-        their owner orders them (wait_stream / a synchronize)."""
-        for t in tensors:
-            if hasattr(t, "data_ptr") and getattr(t, "is_cuda", False):
-                import torch
-                s = torch.cuda.current_stream(t.device)
-                # Nothing in flight on the producer stream: whatever wrote the tensors is done, and there is nothing to order against.
-                # (Round 6: the event record + two stream waits per submit are a barrier packet on the producer's queue and ~10 us of host
-                # time -- a pipelined caller of small MSMs whose producer is torch's legacy null stream measured 0.67 -> 0.80 ms per MSM at
-                # 2^17 pairs with three MSMs in flight because of them; the query is one hipStreamQuery.)
-                if s.query():
-                    return
-                self.wait_stream(s.cuda_stream)
-                return
-
     def wait_stream(self, stream):
         """Everything the engine enqueues from now on waits for the work `stream` (a hipStream_t address) holds now."""
-        if self.L.ctt_hip_msm_wait_stream(self.ctx, ctypes.c_void_p(int(stream))) != 0:
+        if self.L.ctt_hip_msm_wait_stream(self.ctx, ptr(stream)) != 0:
             raise RuntimeError("ctt_hip_msm_wait_stream failed")
 
     def msm(self, curve, d_coefs, d_points, n, coord="aff", fr_coefs=False):
         info = CURVES[curve]
-        nco = 2 if coord == "aff" else 3
-        r = np.zeros(nco * info.coord_bytes, dtype=np.uint8)
-        self._order(d_coefs, d_points)
-        rc = self.L.ctt_hip_msm_device(self.ctx, info.cid, COEF_FR if fr_coefs else COEF_BIG, _out_kind(info, coord), _ptr(r),
-                                       self._dptr(d_coefs), self._dptr(d_points), n)
+        r = result_buffer(info, coord)
+        order(self.L, self.ctx, d_coefs, d_points)
+        rc = self.L.ctt_hip_msm_device(self.ctx, info.cid, COEF_FR if fr_coefs else COEF_BIG, _out_kind(info, coord), ptr(r),
+                                       ptr(d_coefs), ptr(d_points), n)
         if rc != 0:
             raise RuntimeError("ctt_hip_msm_device failed")
         return r
@@ -174,9 +147,9 @@ class DeviceMsm:
     def submit(self, curve, d_coefs, d_points, n, fr_coefs=False):
         """Enqueue one MSM and return a ticket at once (at most three outstanding per curve: a fourth raises)."""
         info = CURVES[curve]
-        self._order(d_coefs, d_points)
+        order(self.L, self.ctx, d_coefs, d_points)
         t = self.L.ctt_hip_msm_device_submit(self.ctx, info.cid, COEF_FR if fr_coefs else COEF_BIG,
-                                             self._dptr(d_coefs), self._dptr(d_points), n)
+                                             ptr(d_coefs), ptr(d_points), n)
         if t < 0:
             raise RuntimeError("ctt_hip_msm_device_submit failed (bad arguments, or three tickets already outstanding)")
         return (curve, t)
@@ -185,9 +158,8 @@ class DeviceMsm:
         """Wait for a submitted MSM, run the host tail, return the result."""
         curve, t = ticket
         info = CURVES[curve]
-        nco = 2 if coord == "aff" else 3
-        r = np.zeros(nco * info.coord_bytes, dtype=np.uint8)
-        if self.L.ctt_hip_msm_device_finish(self.ctx, t, _out_kind(info, coord), _ptr(r)) != 0:
+        r = result_buffer(info, coord)
+        if self.L.ctt_hip_msm_device_finish(self.ctx, t, _out_kind(info, coord), ptr(r)) != 0:
             raise RuntimeError("ctt_hip_msm_device_finish failed (ticket not outstanding)")
         return r
 
@@ -196,14 +168,14 @@ class DeviceMsm:
         self.L.ctt_hip_msm_sync(self.ctx)
 
     def gen_points(self, curve, seed, n, d_out, first=0):
-        self._order(d_out)
-        rc = self.L.ctt_hip_gen_points(self.ctx, CURVES[curve].cid, seed & (2**64 - 1), first, n, self._dptr(d_out))
+        order(self.L, self.ctx, d_out)
+        rc = self.L.ctt_hip_gen_points(self.ctx, CURVES[curve].cid, seed & (2**64 - 1), first, n, ptr(d_out))
         if rc != 0:
             raise RuntimeError("ctt_hip_gen_points failed")
 
     def field_op(self, curve, op, d_a, d_b, d_r, n):
-        self._order(d_a, d_b, d_r)
-        rc = self.L.ctt_hip_field_op(self.ctx, CURVES[curve].cid, op, self._dptr(d_a), self._dptr(d_b), self._dptr(d_r), n)
+        order(self.L, self.ctx, d_a, d_b, d_r)
+        rc = self.L.ctt_hip_field_op(self.ctx, CURVES[curve].cid, op, ptr(d_a), ptr(d_b), ptr(d_r), n)
         if rc != 0:
             raise RuntimeError("ctt_hip_field_op failed")
 
@@ -222,33 +194,31 @@ class DeviceMsm:
         cap = [t.numel() * t.element_size() if t is not None else 0 for t in (d_entries, d_bstart, d_buckets)]
         args = np.array([int(sizing.get(k, 0)) for k in self.SORT_PROBE_IN] + [cap[0] // 4, cap[1] // 4, cap[2]], dtype=np.int32)
         used = np.zeros(len(self.SORT_PROBE_USED), dtype=np.uint32)
-        self._order(d_scalars, d_entries, d_bstart, d_maxcount, d_buckets)
-        rc = self.L.ctt_hip_sort_probe_words(self.ctx, self._dptr(d_scalars), kwords, n, _ptr(args), _ptr(used), self._dptr(d_entries),
-                                             self._dptr(d_bstart), self._dptr(d_maxcount), self._dptr(d_buckets) if d_buckets is not None else None)
+        order(self.L, self.ctx, d_scalars, d_entries, d_bstart, d_maxcount, d_buckets)
+        rc = self.L.ctt_hip_sort_probe_words(self.ctx, ptr(d_scalars), kwords, n, ptr(args), ptr(used), ptr(d_entries),
+                                             ptr(d_bstart), ptr(d_maxcount), ptr(d_buckets))
         return dict(zip(self.SORT_PROBE_USED, (int(x) for x in used))) if rc == 0 else None
 
     def glv_front_probe(self, curve, d_scalars, d_points, n, d_records, d_half):
         """ctt_hip_glv_front_probe: the front kernel of the endomorphism split alone -- n canonical scalars [n][8] and n affine points in,
         the records [2n] and the half scalars [2n][4] out (include/ctt_msm_hip.h).  False when the call was refused (nothing launched)."""
-        self._order(d_scalars, d_points, d_records, d_half)
-        dp = lambda t: self._dptr(t) if t is not None else None
-        return self.L.ctt_hip_glv_front_probe(self.ctx, CURVES[curve].cid, dp(d_scalars), dp(d_points), n, dp(d_records), dp(d_half)) == 0
+        order(self.L, self.ctx, d_scalars, d_points, d_records, d_half)
+        return self.L.ctt_hip_glv_front_probe(self.ctx, CURVES[curve].cid, ptr(d_scalars), ptr(d_points), n, ptr(d_records), ptr(d_half)) == 0
 
     def sum_reduce(self, curve, d_points, n, coord="aff"):
         """r = sum of n affine points resident in HBM (sum_reduce_vartime)."""
         info = CURVES[curve]
-        nco = 2 if coord == "aff" else 3
-        r = np.zeros(nco * info.coord_bytes, dtype=np.uint8)
-        self._order(d_points)
-        if self.L.ctt_hip_sum_reduce(self.ctx, info.cid, _COORD[coord], _ptr(r), self._dptr(d_points), n, 1) != 0:
+        r = result_buffer(info, coord)
+        order(self.L, self.ctx, d_points)
+        if self.L.ctt_hip_sum_reduce(self.ctx, info.cid, _COORD[coord], ptr(r), ptr(d_points), n, 1) != 0:
             raise RuntimeError("ctt_hip_sum_reduce failed")
         return r
 
     def batch_affine(self, curve, d_dst, d_src, n, src_coord="jac"):
         """d_dst[i] = affine(d_src[i]); both in HBM (batchAffine_vartime).  Returns when d_dst is complete."""
-        self._order(d_src, d_dst)
-        if self.L.ctt_hip_batch_affine(self.ctx, CURVES[curve].cid, _COORD[src_coord], self._dptr(d_dst),
-                                       self._dptr(d_src), n, 1) != 0:
+        order(self.L, self.ctx, d_src, d_dst)
+        if self.L.ctt_hip_batch_affine(self.ctx, CURVES[curve].cid, _COORD[src_coord], ptr(d_dst),
+                                       ptr(d_src), n, 1) != 0:
             raise RuntimeError("ctt_hip_batch_affine failed")
 
     def enable_timings(self, on=True):
@@ -258,14 +228,14 @@ class DeviceMsm:
 
     def last_timings(self):
         ms = np.zeros(6, dtype=np.float32)
-        self.L.ctt_hip_msm_last_timings(self.ctx, _ptr(ms), 6)
+        self.L.ctt_hip_msm_last_timings(self.ctx, ptr(ms), 6)
         return dict(zip(("digits", "sort", "accumulate", "merge", "reduce", "total"), (float(x) for x in ms)))
 
     def last_plan(self):
         """c, W = accumulations per input pair (the digit windows of the scalar; twice the bucket sets when the endomorphism split
         ran), K, G, S, lanes, bucket_sets and glv (1 = the split ran)."""
         p = np.zeros(8, dtype=np.int32)
-        self.L.ctt_hip_msm_last_plan(self.ctx, _ptr(p), 8)
+        self.L.ctt_hip_msm_last_plan(self.ctx, ptr(p), 8)
         return dict(zip(("c", "W", "K", "G", "S", "lanes", "bucket_sets", "glv"), (int(x) for x in p)))
 
 
@@ -288,7 +258,7 @@ def subgroup_check(curve, points, ctx=None):
     info = CURVES[curve]
     pts = np.ascontiguousarray(points, dtype=np.uint8).reshape(-1, info.aff_bytes)
     ok = np.zeros(pts.shape[0], dtype=np.uint8)
-    if _lib.lib().ctt_hip_subgroup_check(ctx, info.cid, _ptr(ok), _ptr(pts), pts.shape[0], 0) != 0:
+    if _lib.lib().ctt_hip_subgroup_check(ctx, info.cid, ptr(ok), ptr(pts), pts.shape[0], 0) != 0:
         raise RuntimeError("ctt_hip_subgroup_check failed")
     return ok.astype(bool)
 
@@ -297,9 +267,8 @@ def ec_sum_affine(curve, pts_aff, coord="aff"):
     """Host-only sum of affine points (combining per-GPU partial MSMs)."""
     info = CURVES[curve]
     pts = np.ascontiguousarray(pts_aff, dtype=np.uint8).reshape(-1, info.aff_bytes)
-    nco = 2 if coord == "aff" else 3
-    r = np.zeros(nco * info.coord_bytes, dtype=np.uint8)
-    rc = _lib.lib().ctt_hip_ec_sum_affine(info.cid, _COORD[coord], _ptr(r), _ptr(pts), pts.shape[0])
+    r = result_buffer(info, coord)
+    rc = _lib.lib().ctt_hip_ec_sum_affine(info.cid, _COORD[coord], ptr(r), ptr(pts), pts.shape[0])
     if rc != 0:
         raise RuntimeError("ctt_hip_ec_sum_affine failed")
     return r
@@ -309,9 +278,8 @@ def sum_reduce_vartime(curve, points, coord="jac"):
     """Mirror of sum_reduce_vartime(r, points) (ec_shortweierstrass_batch_ops.nim:649-663), host arrays in, GPU sum."""
     info = CURVES[curve]
     pts = np.ascontiguousarray(points, dtype=np.uint8).reshape(-1, info.aff_bytes)
-    nco = 2 if coord == "aff" else 3
-    r = np.zeros(nco * info.coord_bytes, dtype=np.uint8)
-    if _lib.lib().ctt_hip_sum_reduce(None, info.cid, _COORD[coord], _ptr(r), _ptr(pts), pts.shape[0], 0) != 0:
+    r = result_buffer(info, coord)
+    if _lib.lib().ctt_hip_sum_reduce(None, info.cid, _COORD[coord], ptr(r), ptr(pts), pts.shape[0], 0) != 0:
         raise RuntimeError("ctt_hip_sum_reduce failed")
     return r
 
@@ -323,7 +291,7 @@ def batchAffine_vartime(curve, points, coord="jac"):
     src = np.ascontiguousarray(points, dtype=np.uint8).reshape(-1, 3 * info.coord_bytes)
     dst = np.zeros((src.shape[0], info.aff_bytes), dtype=np.uint8)
     fn = getattr(_lib.lib(), f"ctt_{info.sym}_{coord}_batch_affine")
-    fn(_ptr(dst), _ptr(src), src.shape[0])
+    fn(ptr(dst), ptr(src), src.shape[0])
     return dst
 
 
@@ -343,18 +311,16 @@ class CachedBases:
             import torch
             self.n = int(points.shape[0])
             torch.cuda.current_stream(points.device).synchronize()  # the records are made from the tensor as it is now
-            ptr = ctypes.c_void_p(points.data_ptr())
         else:
             points = np.ascontiguousarray(points, dtype=np.uint8)
             if points.ndim != 2 or points.shape[1] != self.info.aff_bytes:
                 raise ValueError(f"points must have shape (n, {self.info.aff_bytes})")
             self.n = points.shape[0]
-            ptr = _ptr(points)
         if table:
-            self.handle = self.L.ctt_hip_msm_bases_create_table(ctx, self.info.cid, ptr, self.n, 1 if on_device else 0,
+            self.handle = self.L.ctt_hip_msm_bases_create_table(ctx, self.info.cid, ptr(points), self.n, 1 if on_device else 0,
                                                                 int(window_bits))
         else:
-            self.handle = self.L.ctt_hip_msm_bases_create(ctx, self.info.cid, ptr, self.n, 1 if on_device else 0)
+            self.handle = self.L.ctt_hip_msm_bases_create(ctx, self.info.cid, ptr(points), self.n, 1 if on_device else 0)
         if not self.handle:
             raise RuntimeError("ctt_hip_msm_bases_create failed")
         self.window_bits = self.L.ctt_hip_msm_bases_window_bits(self.handle)  # 0 = plain records
@@ -364,36 +330,31 @@ class CachedBases:
         DeviceMsm.finish / CachedBases.finish (at most three outstanding per curve)."""
         if n > self.n:
             raise AssertionError("more coefficients than cached bases")
-        if hasattr(d_coefs, "data_ptr") and getattr(d_coefs, "is_cuda", False):
-            import torch
-            if self.L.ctt_hip_msm_wait_stream(self.ctx, ctypes.c_void_p(torch.cuda.current_stream(d_coefs.device).cuda_stream)) != 0:
-                raise RuntimeError("ctt_hip_msm_wait_stream failed")
+        order(self.L, self.ctx, d_coefs)
         t = self.L.ctt_hip_msm_with_bases_submit(self.ctx, self.handle, COEF_FR if fr_coefs else COEF_BIG,
-                                                 DeviceMsm._dptr(d_coefs), n)
+                                                 ptr(d_coefs), n)
         if t < 0:
             raise RuntimeError("ctt_hip_msm_with_bases_submit failed (wrong context, or three tickets already outstanding)")
         return (self.curve, t)
 
     def finish(self, ticket, coord="prj"):
         curve, t = ticket
-        nco = 2 if coord == "aff" else 3
-        r = np.zeros(nco * self.info.coord_bytes, dtype=np.uint8)
-        if self.L.ctt_hip_msm_device_finish(self.ctx, t, _out_kind(self.info, coord), _ptr(r)) != 0:
+        r = result_buffer(self.info, coord)
+        if self.L.ctt_hip_msm_device_finish(self.ctx, t, _out_kind(self.info, coord), ptr(r)) != 0:
             raise RuntimeError("ctt_hip_msm_device_finish failed (ticket not outstanding)")
         return r
 
     def msm(self, coefs, coord="prj", fr_coefs=False):
-        if hasattr(coefs, "data_ptr") and getattr(coefs, "is_cuda", False):
+        if is_cuda(coefs):
             return self.finish(self.submit(coefs, int(coefs.shape[0]), fr_coefs=fr_coefs), coord=coord)
         coefs = np.ascontiguousarray(coefs, dtype=np.uint8)
         if coefs.ndim != 2 or coefs.shape[1] != 32:
             raise ValueError("coefs must have shape (n, 32)")
         if coefs.shape[0] > self.n:
             raise AssertionError("more coefficients than cached bases")
-        nco = 2 if coord == "aff" else 3
-        r = np.zeros(nco * self.info.coord_bytes, dtype=np.uint8)
-        rc = self.L.ctt_hip_msm_with_bases(self.ctx, self.handle, COEF_FR if fr_coefs else COEF_BIG, _out_kind(self.info, coord), _ptr(r),
-                                           _ptr(coefs), coefs.shape[0], 0)
+        r = result_buffer(self.info, coord)
+        rc = self.L.ctt_hip_msm_with_bases(self.ctx, self.handle, COEF_FR if fr_coefs else COEF_BIG, _out_kind(self.info, coord), ptr(r),
+                                           ptr(coefs), coefs.shape[0], 0)
         if rc != 0:
             raise RuntimeError("ctt_hip_msm_with_bases failed")
         return r

@@ -16,6 +16,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from ._arrays import ptr
 from .curves import CURVES
 
 INVERSE, IN_BRP, OUT_BRP, IN_MONT, OUT_MONT = 1, 2, 4, 8, 16
@@ -81,7 +82,7 @@ class NttPlan:
 
     def ntt_ptr(self, d_out, d_in, batch, flags=0, shift=None):
         """the C call on raw device addresses; -> its return value"""
-        return self.L.ctt_hip_fr_ntt(self.ctx, self.plan, ctypes.c_void_p(int(d_out)), ctypes.c_void_p(int(d_in)), int(batch), int(flags),
+        return self.L.ctt_hip_fr_ntt(self.ctx, self.plan, ptr(d_out), ptr(d_in), int(batch), int(flags),
                                      None if shift is None else _scalar(shift))
 
     def ntt(self, x, inverse=False, in_brp=False, out_brp=False, in_mont=False, out_mont=False, shift=None, out=None):

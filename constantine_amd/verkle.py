@@ -16,11 +16,10 @@ with Z = 1, "ser" (m, 32) big-endian, "fr" (m, 32) Montgomery.  Like the referen
 Banderwagon elements.  Shape errors raise ValueError before the library is touched; a call the GPU cannot serve raises
 GpuUnavailable, any other refusal MsmRefused.
 """
-import ctypes
-
 import numpy as np
 
 from . import _lib
+from ._arrays import is_cuda, order, ptr
 from .msm import MsmRefused
 
 _WANT = ("prj", "ser", "fr")
@@ -29,13 +28,9 @@ _BYTES = {"prj": 96, "ser": 32, "fr": 32, "dfr": 32}
 MAX_BASES = 256
 
 
-def _is_cuda(a):
-    return hasattr(a, "data_ptr") and getattr(a, "is_cuda", False)
-
-
 def _shaped(a, tail, what):
     """`a` as a contiguous uint8 array / tensor whose trailing dimensions are `tail`"""
-    if _is_cuda(a):
+    if is_cuda(a):
         import torch
         if a.dtype != torch.uint8:
             raise ValueError(f"{what} must be a uint8 tensor")
@@ -47,14 +42,8 @@ def _shaped(a, tail, what):
     return a
 
 
-def _ptr(a):
-    if a is None:
-        return ctypes.c_void_p(0)
-    return ctypes.c_void_p(a.data_ptr()) if _is_cuda(a) else a.ctypes.data_as(ctypes.c_void_p)
-
-
 def _empty_like(src, m, width):
-    if _is_cuda(src):
+    if is_cuda(src):
         import torch
         return torch.empty((m, width), dtype=torch.uint8, device=src.device)
     return np.zeros((m, width), dtype=np.uint8)
@@ -66,21 +55,12 @@ def _refused(L, rc, what):
     raise MsmRefused(rc)
 
 
-def _order(L, ctx, a):
-    """the engine's stream waits for what torch's current stream holds for a CUDA tensor (msm.DeviceMsm._order)"""
-    if _is_cuda(a):
-        import torch
-        s = torch.cuda.current_stream(a.device)
-        if not s.query() and L.ctt_hip_msm_wait_stream(ctx, ctypes.c_void_p(s.cuda_stream)) != 0:
-            raise RuntimeError("ctt_hip_msm_wait_stream failed")
-
-
 class VerkleCrs:
     """A table of precomputed multiples of n <= 256 Banderwagon points, resident on the GPU (ctt_hip_verkle_crs_*).
     window_bits: 0 = the library's default, else 2 .. 10.  `ctx` is a ctt_hip_msm_ctx* (DeviceMsm.ctx) or None for the default context."""
 
     def __init__(self, points, ctx=None, window_bits=0, on_device=False):
-        if on_device != _is_cuda(points):
+        if on_device != is_cuda(points):
             raise ValueError("on_device=True takes a CUDA tensor, on_device=False a host array")
         points = _shaped(points, (64,), "points")
         n = int(points.shape[0])
@@ -95,7 +75,7 @@ class VerkleCrs:
         if on_device:
             import torch
             torch.cuda.current_stream(points.device).synchronize()   # the table is made from the tensor as it is now
-        self.handle = self.L.ctt_hip_verkle_crs_create(ctx, _ptr(points), n, int(window_bits), 1 if on_device else 0)
+        self.handle = self.L.ctt_hip_verkle_crs_create(ctx, ptr(points), n, int(window_bits), 1 if on_device else 0)
         if not self.handle:
             _refused(self.L, -1, "ctt_hip_verkle_crs_create")
         self.window_bits = self.L.ctt_hip_verkle_crs_window_bits(self.handle)
@@ -113,9 +93,9 @@ class VerkleCrs:
         out = {w: _empty_like(coefs, m, _BYTES[w]) for w in _WANT if w in want}
         if m == 0:
             return out
-        _order(self.L, self.ctx, coefs)
-        rc = self.L.ctt_hip_verkle_commit_batch(self.ctx, self.handle, 1 if fr_coefs else 0, _ptr(out.get("prj")), _ptr(out.get("ser")),
-                                                _ptr(out.get("fr")), _ptr(coefs), m, 1 if _is_cuda(coefs) else 0)
+        order(self.L, self.ctx, coefs)
+        rc = self.L.ctt_hip_verkle_commit_batch(self.ctx, self.handle, 1 if fr_coefs else 0, ptr(out.get("prj")), ptr(out.get("ser")),
+                                                ptr(out.get("fr")), ptr(coefs), m, 1 if is_cuda(coefs) else 0)
         if rc != 0:
             _refused(self.L, rc, "ctt_hip_verkle_commit_batch")
         return out
@@ -141,12 +121,12 @@ class VerkleCrs:
         if E and (int(idx.min()) < 0 or int(idx.max()) >= self.n):
             raise ValueError(f"idx holds indices in [0, {self.n})")
         if base is not None:
-            if _is_cuda(base) != _is_cuda(deltas):
+            if is_cuda(base) != is_cuda(deltas):
                 raise ValueError("base and deltas are both host arrays or both CUDA tensors")
             base = _shaped(base, (96,), "base")
             if int(base.shape[0]) != m:
                 raise ValueError(f"base has {int(base.shape[0])} rows, row_ptr {m}")
-            if _is_cuda(base) and base.device != deltas.device:
+            if is_cuda(base) and base.device != deltas.device:
                 raise ValueError("base and deltas are on different devices")
         if not self.handle:
             raise ValueError("this VerkleCrs is closed")
@@ -155,11 +135,10 @@ class VerkleCrs:
         out = {w: _empty_like(deltas, m, _BYTES[w]) for w in _WANT_UPDATE if w in want}
         if m == 0:
             return out
-        _order(self.L, self.ctx, deltas)
-        _order(self.L, self.ctx, base)
-        rc = self.L.ctt_hip_verkle_update_batch(self.ctx, self.handle, 1 if fr_coefs else 0, _ptr(out.get("prj")), _ptr(out.get("ser")),
-                                                _ptr(out.get("fr")), _ptr(out.get("dfr")), _ptr(base), _ptr(row_ptr), _ptr(idx),
-                                                _ptr(deltas), m, 1 if _is_cuda(deltas) else 0)
+        order(self.L, self.ctx, deltas, base)   # both on one device: one current stream
+        rc = self.L.ctt_hip_verkle_update_batch(self.ctx, self.handle, 1 if fr_coefs else 0, ptr(out.get("prj")), ptr(out.get("ser")),
+                                                ptr(out.get("fr")), ptr(out.get("dfr")), ptr(base), ptr(row_ptr), ptr(idx),
+                                                ptr(deltas), m, 1 if is_cuda(deltas) else 0)
         if rc != 0:
             _refused(self.L, rc, "ctt_hip_verkle_update_batch")
         return out
@@ -167,7 +146,7 @@ class VerkleCrs:
     def last_timings(self):
         """ms of the context's last commit (or update) batch (after DeviceMsm.enable_timings) and of its last table build"""
         ms = np.zeros(3, dtype=np.float32)
-        self.L.ctt_hip_verkle_last_timings(self.ctx, ms.ctypes.data_as(ctypes.c_void_p), 3)
+        self.L.ctt_hip_verkle_last_timings(self.ctx, ptr(ms), 3)
         return dict(zip(("commit", "finish", "table"), (float(x) for x in ms)))
 
     def close(self):
@@ -189,8 +168,8 @@ def _finish(symbol, points_prj, ctx):
     if m == 0:
         return out
     L = _lib.lib()
-    _order(L, ctx, points_prj)
-    rc = getattr(L, symbol)(ctx, _ptr(out), _ptr(points_prj), m, 1 if _is_cuda(points_prj) else 0)
+    order(L, ctx, points_prj)
+    rc = getattr(L, symbol)(ctx, ptr(out), ptr(points_prj), m, 1 if is_cuda(points_prj) else 0)
     if rc != 0:
         _refused(L, rc, symbol)
     return out

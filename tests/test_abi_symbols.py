@@ -10,10 +10,137 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _preprocessed(header):
+    """the header after the C preprocessor (its declaration macros expanded), white space collapsed"""
+    out = subprocess.check_output(["gcc", "-E", "-P", os.path.join(ROOT, "include", header)], text=True)
+    return " ".join(out.split())
+
+
 def _declared_symbols():
     """Expand the declaration macros of the header with the C preprocessor and pull the function names."""
-    out = subprocess.check_output(["gcc", "-E", "-P", os.path.join(ROOT, "include", "ctt_msm_hip.h")], text=True)
-    return sorted(set(re.findall(r"\b(ctt_[a-z0-9_]+)\s*\(", out)))
+    return sorted(set(re.findall(r"\b(ctt_[a-z0-9_]+)\s*\(", _preprocessed("ctt_msm_hip.h"))))
+
+
+# A prototype as kinds: "void", "ptr", or (signed?, bytes) of an integer passed by value.
+_C_INTEGERS = {"int": (True, 4), "size_t": (False, 8), "uint32_t": (False, 4), "uint64_t": (False, 8)}
+
+
+def _declared_prototypes(header):
+    """{name: (kind of the return value, [kind of each parameter])} of every ctt_* function `header` declares"""
+    text = _preprocessed(header)
+    integers = dict(_C_INTEGERS)
+    for enum in re.findall(r"typedef enum __attribute__\(\(__packed__\)\) \{[^}]*\} (\w+) ?;", text):
+        integers[enum] = (False, 1)                   # the reference's status enums: one byte
+
+    def kind(decl, is_param):
+        if "*" in decl or "[" in decl:
+            return "ptr"
+        words = [w for w in decl.split() if w != "const"]
+        if is_param and len(words) > 1:
+            words = words[:-1]                        # the parameter's name
+        assert len(words) == 1, decl
+        return "void" if words[0] == "void" else integers[words[0]]
+
+    protos = {}
+    for ret, name, params in re.findall(r"(?:^|(?<=[;}])) ?([\w\s\*]+?)\b(ctt_[a-z0-9_]+) ?\(([^()]*)\) ?;", text):
+        assert name not in protos, name
+        params = [] if params.strip() == "void" else params.split(",")
+        protos[name] = (kind(ret, False), [kind(p, True) for p in params])
+    return protos
+
+
+def _ctypes_kind(t):
+    if t is None:
+        return "void"
+    if issubclass(t, (ctypes._Pointer, ctypes.c_void_p, ctypes.c_char_p)):
+        return "ptr"
+    assert issubclass(t, ctypes._SimpleCData) and t._type_ in "bhilqBHILQ", t   # c_size_t IS c_uint64 or c_ulong: compare by kind and size
+    return (t._type_.islower(), ctypes.sizeof(t))
+
+
+class _FakeFunction:
+    """what ctypes.CDLL hands out for a symbol, with defaults no prototype of the tables has"""
+    restype = argtypes = "unset"
+
+
+class _FakeCDLL:
+    """stands in for ctypes.CDLL: exports every name but `lacks`, loads nothing"""
+    lacks = ()
+
+    def __init__(self, path, *a, **k):
+        self._path = path
+
+    def __getattr__(self, name):
+        if name.startswith("_") or name in self.lacks:
+            raise AttributeError(name)
+        fn = _FakeFunction()
+        setattr(self, name, fn)
+        return fn
+
+
+@pytest.fixture
+def fake_cdll(monkeypatch):
+    """_lib.lib() / banderwagon_lib() over _FakeCDLL; the real libraries load again afterwards"""
+    from constantine_amd import _lib
+
+    class Fake(_FakeCDLL):
+        pass
+    monkeypatch.setattr(ctypes, "CDLL", Fake)
+    monkeypatch.setattr(_lib, "LIB_PATH", __file__)           # any file that exists
+    monkeypatch.setattr(_lib, "BW_LIB_PATH", __file__)
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib, "_bw_lib", None)
+    monkeypatch.delenv("CTT_MSM_HIP_LIB", raising=False)
+    monkeypatch.delenv("CTT_MSM_HIP_ALLOW_OLD_ABI", raising=False)
+    return Fake
+
+
+def test_prototype_tables_agree_with_the_headers():
+    """Every ctt_* declaration of both headers, reduced to kinds (pointer; int, size_t, uint32_t, uint64_t; the one-byte packed status
+    enums; void), against the (restype, argtypes) tables that _lib.lib() and _lib.banderwagon_lib() apply: the same names, and for
+    every name the same kinds in the same order.  Needs neither the built library nor a GPU."""
+    from constantine_amd import _lib
+    for header, table, count in (("ctt_msm_hip.h", _lib.PROTOTYPES, 145), ("ctt_msm_hip_banderwagon.h", _lib.BW_PROTOTYPES, 4)):
+        declared = _declared_prototypes(header)
+        assert len(declared) == count, header
+        assert set(table) == set(declared), sorted(set(table) ^ set(declared))
+        for name, (restype, argtypes) in table.items():
+            got = (_ctypes_kind(restype), [_ctypes_kind(t) for t in argtypes])
+            assert got == declared[name], (name, got, declared[name])
+    assert sorted(_declared_prototypes("ctt_msm_hip.h")) == _declared_symbols()
+    assert _lib.exported_symbols() == list(_lib.PROTOTYPES)
+
+
+def test_every_symbol_gets_a_complete_prototype(fake_cdll):
+    """after lib() / banderwagon_lib() no symbol of the tables is left with ctypes' defaults (restype int, argtypes unchecked)"""
+    from constantine_amd import _lib
+    for L, table in ((_lib.lib(), _lib.PROTOTYPES), (_lib.banderwagon_lib(), _lib.BW_PROTOTYPES)):
+        assert isinstance(L, fake_cdll)
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(L, name)
+            assert fn.restype is restype and fn.restype != "unset", name
+            assert fn.argtypes is not None and fn.argtypes != "unset" and list(fn.argtypes) == list(argtypes), name
+
+
+def test_old_abi_opt_in_is_per_symbol(fake_cdll, monkeypatch):
+    """A library that lacks one symbol: an error at load that names it -- unless it is named explicitly (CTT_MSM_HIP_LIB) together
+    with CTT_MSM_HIP_ALLOW_OLD_ABI=1; then it loads, every other symbol has its prototype, and calling the absent one raises."""
+    from constantine_amd import _lib
+    absent = "ctt_hip_verkle_commit_batch"        # not the first of its part of the header
+    fake_cdll.lacks = (absent,)
+    with pytest.raises(AttributeError, match=f"does not export {absent} .*CTT_MSM_HIP_ALLOW_OLD_ABI=1"):
+        _lib.lib()
+    assert _lib._lib is None
+    monkeypatch.setenv("CTT_MSM_HIP_ALLOW_OLD_ABI", "1")        # alone it is not enough
+    with pytest.raises(AttributeError, match=absent):
+        _lib.lib()
+    monkeypatch.setenv("CTT_MSM_HIP_LIB", __file__)
+    L = _lib.lib()
+    with pytest.raises(AttributeError, match=rf"\(old ABI\) has no {absent}"):
+        L.ctt_hip_verkle_commit_batch(None, None, 0, None, None, None, None, 0, 0)
+    for name, (restype, argtypes) in _lib.PROTOTYPES.items():
+        if name != absent:
+            assert getattr(L, name).restype is restype and getattr(L, name).argtypes == argtypes, name
 
 
 def test_header_compiles_as_c_and_layouts():

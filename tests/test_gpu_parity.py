@@ -1280,7 +1280,8 @@ def test_last_plan_of_every_submit_form(torch_cuda):
     Both depend on the curve's width and c only; K, G, S and the lanes are the device's business."""
     import ctypes
     from constantine_amd import CachedBases, DeviceMsm
-    from constantine_amd.msm import COEF_BIG, _out_kind, _ptr
+    from constantine_amd._arrays import ptr
+    from constantine_amd.msm import COEF_BIG, _out_kind
     torch = torch_cuda
     name, n = "pallas", 3000
     curve = po.CURVES[name]
@@ -1299,7 +1300,7 @@ def test_last_plan_of_every_submit_form(torch_cuda):
         def with_device_coefs(bases):   # ctt_hip_msm_with_bases, coefs_on_device = 1 (CachedBases.msm takes the ticket form for a tensor)
             r = np.zeros(2 * bases.info.coord_bytes, dtype=np.uint8)
             torch.cuda.current_stream().synchronize()
-            rc = eng.L.ctt_hip_msm_with_bases(eng.ctx, bases.handle, COEF_BIG, _out_kind(bases.info, "aff"), _ptr(r),
+            rc = eng.L.ctt_hip_msm_with_bases(eng.ctx, bases.handle, COEF_BIG, _out_kind(bases.info, "aff"), ptr(r),
                                               ctypes.c_void_p(ds.data_ptr()), n, 1)
             assert rc == 0
             return r

@@ -11,7 +11,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 from constantine_amd import CURVES, DeviceMsm, _lib  # noqa: E402
-from constantine_amd.msm import _ptr  # noqa: E402
+from constantine_amd._arrays import ptr  # noqa: E402
 
 L = _lib.lib()
 P = {"bls12_381_g1": 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab,
@@ -33,12 +33,12 @@ for name in ("bls12_381_g1", "bn254_snarks_g1"):
         dst = np.zeros((n, info.aff_bytes), dtype=np.uint8)
         fn = getattr(L, f"ctt_{info.sym}_jac_batch_affine")
         for _ in range(2):
-            fn(_ptr(dst), _ptr(jac), n)
+            fn(ptr(dst), ptr(jac), n)
         assert bytes(dst) == bytes(aff)
         ts = []
         for _ in range(7):
             t0 = time.perf_counter()
-            fn(_ptr(dst), _ptr(jac), n)
+            fn(ptr(dst), ptr(jac), n)
             ts.append((time.perf_counter() - t0) * 1e3)
         print(f"ctt_{info.sym}_jac_batch_affine, 2^{lg} points on the host: {statistics.median(ts):.3f} ms (min {min(ts):.3f}); "
               f"{n * (3 * cb + 2 * cb) / 1e6:.0f} MB over the link", flush=True)
