@@ -1,5 +1,6 @@
 """The scalar-field NTT of ctt_hip_fr_ntt in Python integers (test infrastructure): a recursive transform, every flag, the
 fields' moduli and roots of unity, and the case list the CPU harness test and the GPU test share."""
+import functools
 import random
 
 R = 1 << 256   # the Montgomery radix of the 8-word fields
@@ -123,6 +124,37 @@ def cases(field):
         out.append(("in_place_inv_shift_n%d" % (1 << lg), lg, t, 2, INVERSE | IN_BRP | OUT_BRP | IN_MONT, "rand", True))
     lim = two_adicity(p)
     return [c for c in out if c[1] <= lim and (c[5] != "w2n" or c[1] + 1 <= lim)]
+
+
+def large_cases(field):
+    """cases() continued above n = 4096, where the width of an index shows: twiddle exponents of 12 bits and more, power tables
+    longer than 4096, more than a few tile bits on either side of a pass's rows.  2^13 and 2^14 at the default tile in every order,
+    direction and with both shift tables, 2^14 at the largest image and in four passes, 2^16 (two full default passes) and 2^17
+    (the smallest three-pass default plan) on one field each: the recursive reference costs a second per row there."""
+    p = FIELDS[field][2]
+    S = INVERSE | IN_BRP
+    out = [
+        ("n8192_dif", 13, 0, 1, OUT_BRP, None, False), ("n8192_dit", 13, 0, 1, IN_BRP, None, False),
+        ("n8192_inverse", 13, 0, 1, INVERSE, None, False), ("n8192_shift", 13, 0, 1, 0, "rand", False),
+        ("n8192_inverse_shift_in_place", 13, 0, 1, S, "rand", True), ("n8192_batch2", 13, 0, 2, IN_BRP | OUT_BRP, None, False),
+        ("n16384_dif", 14, 0, 1, 0, None, False), ("n16384_dit_batch2", 14, 0, 2, IN_BRP, None, False),
+        ("n16384_inverse", 14, 0, 1, S | OUT_BRP, None, False), ("n16384_shift", 14, 0, 1, OUT_BRP, "rand", False),
+        ("n16384_inverse_shift", 14, 0, 1, INVERSE, "rand", False), ("n16384_in_place", 14, 0, 1, OUT_BRP, None, True),
+        ("t9_n16384_largest_image", 14, 9, 1, OUT_BRP, None, False), ("t9_n16384_dit_inverse_shift", 14, 9, 1, S, "rand", False),
+        ("t4_n16384_four_passes", 14, 4, 1, OUT_BRP, "rand", False), ("t4_n16384_dit", 14, 4, 1, IN_BRP, None, False),
+    ]
+    if field == "bls12_381_fr":
+        out.append(("n65536_two_full_passes", 16, 0, 1, OUT_BRP, "rand", False))
+    if field == "bn254_snarks_fr":
+        out += [("n131072_three_passes", 17, 0, 1, OUT_BRP, None, False), ("n131072_three_passes_dit", 17, 0, 1, IN_BRP, None, False)]
+    lim = two_adicity(p)
+    return [c for c in out if c[1] <= lim]
+
+
+@functools.lru_cache(maxsize=None)
+def large_case_data(field, case):
+    """case_data, computed once for the CPU harness test and the GPU test of one session"""
+    return case_data(field, case)
 
 
 def case_data(field, case):
