@@ -413,7 +413,7 @@ __global__ void __launch_bounds__(EC_BLOCK) k_pyr_quad(PyrArgs<F> a, uint32_t nt
   // The narrow passes are a chain of short dependent launches of few waves which, when MSMs are pipelined, share their SIMDs with the next MSM's
   // sort and accumulate kernels; at equal wave priority the chain -- the critical path of a small MSM -- stretches.  s_setprio 3 lets these waves
   // issue first: BLS12-381 G1 -5 ... -6 % per MSM at 2^14 ... 2^18 pairs with two in flight, BN254 -5 ... -9 % at 2^16 ... 2^19; level from 2^20 on,
-  // and the host switches it off there and for the curves it does not help (Curve::NARROW_PRIO_LOG2N, profiles/wave_priority_r06.txt).
+  // and the host switches it off there and for the curves it does not help (CurveTuning::narrow_prio_log2n, profiles/wave_priority_r06.txt).
   if (prio) __builtin_amdgcn_s_setprio(3);
   const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t t = lane >> 2;

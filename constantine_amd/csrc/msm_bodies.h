@@ -31,39 +31,120 @@ static constexpr uint32_t KEY_NONE = 0xffffffffu;
 // ---------------------------------------------------------------------------------------------
 // F  = coordinate field in the reference's representation (what the C API hands over and takes back)
 // FD = coordinate field the kernels compute in (carry-free limbs where that is faster, see fpu.h)
-// ACC_NS / RED_NS: ns per mixed addition of the accumulate kernel and per full addition of the reduction passes with the whole
+// The curve's measured figures, one aggregate per descriptor (TUNE); msm_place.h decides by them.
+// acc_ns / red_ns: ns per mixed addition of the accumulate kernel and per full addition of the reduction passes with the whole
 // chip busy, measured on MI355X (profiles/): what the window-size cost model (msm_plan.h choose_window_bits) ranks plans by.
-// NARROW_PRIO_LOG2N: the narrow reduction passes run at raised wave priority (hip_backend.h k_pyr_quad) for MSMs of up to 2^this pairs, 0 = never;
+// narrow_prio_log2n: the narrow reduction passes run at raised wave priority (hip_backend.h k_pyr_quad) for MSMs of up to 2^this pairs, 0 = never;
 // measured per curve (profiles/wave_priority_r06.txt: it helps BLS12-381 G1 and BN254 up to 2^19, does nothing for G2 and costs Pallas 3 % at 2^16).
-// WHOLE_TAIL_LOG2N: from 2^this pairs on the accumulation of a pipelined MSM waits for the WHOLE tail of the previous one instead of its wide passes only
-// (msm_pipeline.h accumulate_pairs), 0 = never: the accumulate kernels of the 9-limb curves own every register of the chip (4 waves x 128), a narrow pass
+// whole_tail_log2n: from 2^this pairs on the accumulation of a pipelined MSM waits for the WHOLE tail of the previous one instead of its wide passes only
+// (msm_place.h place_accum), 0 = never: the accumulate kernels of the 9-limb curves own every register of the chip (4 waves x 128), a narrow pass
 // beside them crawls (2 ms instead of 7 us) and costs the accumulation 19 % -- Pallas / Vesta 2^22 5.58 -> 5.02 ms per MSM, BN254 2^21 3.03 -> 2.76
 // (profiles/whole_tail_wait_r06.txt); BLS12-381 G1 leaves registers free and loses 5-19 % when made to wait.
-// GLV_LOG2N / GLV_MAX_LOG2N: a device-resident MSM without cached bases of 2^GLV_LOG2N .. 2^GLV_MAX_LOG2N pairs runs the endomorphism split
+// glv_log2n / glv_max_log2n: a device-resident MSM without cached bases of 2^glv_log2n .. 2^glv_max_log2n pairs runs the endomorphism split
 // (bls12_381_glv_split below: two 127-bit half scalars per pair, half the bucket sets), 0 = never -- every curve but BLS12-381 G1.  Measured
 // (profiles/glv_split_r07.txt, ms per MSM with two in flight, without / with): 2^17 0.586 / 0.563, 2^18 0.930 / 0.866, 2^19 1.62 / 1.51, 2^20 2.754 /
 // 2.710 (A/B of two libraries), 2^21 5.51 / 5.44 -- and 2^15 0.362 / 0.385, 2^16 0.421 / 0.428, 2^22 10.24 / 10.46: what the split saves is half a
 // bucket reduction, a constant; what it costs (twice the records written, a slower sort) grows with the pairs.  The option "glv" overrides both.
-// ACCUM_HANDOVER / ACCUM_HANDOVER_LOG2N: from 2^LOG2N pairs on the waves of the accumulate kernel start at raised priority and drop it
-// max(ACCUM_HANDOVER, K / 8) iterations before their end, so that the waves of a SIMD finish together instead of one after the other
-// (hip_backend.h k_accum; msm_pipeline.h accum_handover), 0 = never.  Measured (profiles/accum_handover_r08.txt, ms per MSM with two in flight,
+// accum_handover / accum_handover_log2n: from 2^log2n pairs on the waves of the accumulate kernel start at raised priority and drop it
+// max(accum_handover, K / 8) iterations before their end, so that the waves of a SIMD finish together instead of one after the other
+// (hip_backend.h k_accum; msm_place.h place_accum), 0 = never.  Measured (profiles/accum_handover_r08.txt, ms per MSM with two in flight,
 // off / on): BLS12-381 G1 2^19 1.53 / 1.50, 2^20 2.82 / 2.73, 2^21 5.57 / 5.28, 2^22 10.58 / 10.06 -- and 2^18 0.90 / 0.94: below the bound the
 // previous MSM's tail, outranked beside the accumulation, is what the step waits for.  BN254 2^20 1.58 / 1.54, 2^22 5.33 / 5.10, but 2^19 0.90 /
 // 0.98; Pallas 2^20 1.417 / 1.392, Vesta 2^20 1.343 / 1.314.  The distance: a wave that yields keeps advancing in the slots its partner leaves
 // (about a tenth of them), so a short distance is used up before the partner has caught up -- 2, 4 and 8 do nothing for BLS12-381 G1 at
 // K = 128 -- and a long one is a long stretch alone at the end; the best measured is 32 at K = 64 .. 256 and 64 at K = 512.  The G2 curves (one
 // wave per SIMD) and Banderwagon (not measured) stay off.  The option "accum_handover" overrides.
-struct Bls12381G1 { using F = Fp<BLS12_381_Fp>; using FD = FpU<BLS12_381_Fp_U>; using Fr = Fp<BLS12_381_Fr>; static constexpr int BITS = 255; static constexpr int ID = 0; static constexpr double ACC_NS = 0.142, RED_NS = 0.26; static constexpr int NARROW_PRIO_LOG2N = 19; static constexpr int GLV_LOG2N = 17, GLV_MAX_LOG2N = 21; static constexpr int WHOLE_TAIL_LOG2N = 0; static constexpr int ACCUM_HANDOVER = 32, ACCUM_HANDOVER_LOG2N = 19; };
-struct Bls12381G2 { using F = Fp2<Fp<BLS12_381_Fp>>; using FD = Fp2<FpU<BLS12_381_Fp_U>>; using Fr = Fp<BLS12_381_Fr>; static constexpr int BITS = 255; static constexpr int ID = 1; static constexpr double ACC_NS = 0.467, RED_NS = 1.1; static constexpr int NARROW_PRIO_LOG2N = 0; static constexpr int GLV_LOG2N = 0, GLV_MAX_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 0; static constexpr int ACCUM_HANDOVER = 0, ACCUM_HANDOVER_LOG2N = 0; };
-struct Bn254G1 { using F = Fp<BN254_Fp>; using FD = FpU<BN254_Fp_U>; using Fr = Fp<BN254_Fr>; static constexpr int BITS = 254; static constexpr int ID = 2; static constexpr double ACC_NS = 0.0685, RED_NS = 0.12; static constexpr int NARROW_PRIO_LOG2N = 19; static constexpr int GLV_LOG2N = 0, GLV_MAX_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 21; static constexpr int ACCUM_HANDOVER = 16, ACCUM_HANDOVER_LOG2N = 20; };
-struct Bn254G2 { using F = Fp2<Fp<BN254_Fp>>; using FD = F; using Fr = Fp<BN254_Fr>; static constexpr int BITS = 254; static constexpr int ID = 3; static constexpr double ACC_NS = 0.5, RED_NS = 1.2; static constexpr int NARROW_PRIO_LOG2N = 0; static constexpr int GLV_LOG2N = 0, GLV_MAX_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 0; static constexpr int ACCUM_HANDOVER = 0, ACCUM_HANDOVER_LOG2N = 0; };
-struct PallasEc { using F = Fp<Pallas_Fp>; using FD = FpU<Pallas_Fp_U>; using Fr = Fp<Vesta_Fp>; static constexpr int BITS = 255; static constexpr int ID = 4; static constexpr double ACC_NS = 0.056, RED_NS = 0.10; static constexpr int NARROW_PRIO_LOG2N = 0; static constexpr int GLV_LOG2N = 0, GLV_MAX_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 21; static constexpr int ACCUM_HANDOVER = 16, ACCUM_HANDOVER_LOG2N = 20; };
-struct VestaEc { using F = Fp<Vesta_Fp>; using FD = FpU<Vesta_Fp_U>; using Fr = Fp<Pallas_Fp>; static constexpr int BITS = 255; static constexpr int ID = 5; static constexpr double ACC_NS = 0.056, RED_NS = 0.10; static constexpr int NARROW_PRIO_LOG2N = 0; static constexpr int GLV_LOG2N = 0, GLV_MAX_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 21; static constexpr int ACCUM_HANDOVER = 16, ACCUM_HANDOVER_LOG2N = 20; };
+struct CurveTuning {
+  double acc_ns;
+  double red_ns;
+  int narrow_prio_log2n;
+  int glv_log2n;
+  int glv_max_log2n;
+  int whole_tail_log2n;
+  int accum_handover;
+  int accum_handover_log2n;
+};
+struct Bls12381G1 { using F = Fp<BLS12_381_Fp>; using FD = FpU<BLS12_381_Fp_U>; using Fr = Fp<BLS12_381_Fr>; static constexpr int BITS = 255; static constexpr int ID = 0;
+  static constexpr CurveTuning TUNE = {
+      /*acc_ns*/ 0.142,
+      /*red_ns*/ 0.26,
+      /*narrow_prio_log2n*/ 19,
+      /*glv_log2n*/ 17,
+      /*glv_max_log2n*/ 21,
+      /*whole_tail_log2n*/ 0,
+      /*accum_handover*/ 32,
+      /*accum_handover_log2n*/ 19};
+};
+struct Bls12381G2 { using F = Fp2<Fp<BLS12_381_Fp>>; using FD = Fp2<FpU<BLS12_381_Fp_U>>; using Fr = Fp<BLS12_381_Fr>; static constexpr int BITS = 255; static constexpr int ID = 1;
+  static constexpr CurveTuning TUNE = {
+      /*acc_ns*/ 0.467,
+      /*red_ns*/ 1.1,
+      /*narrow_prio_log2n*/ 0,
+      /*glv_log2n*/ 0,
+      /*glv_max_log2n*/ 0,
+      /*whole_tail_log2n*/ 0,
+      /*accum_handover*/ 0,
+      /*accum_handover_log2n*/ 0};
+};
+struct Bn254G1 { using F = Fp<BN254_Fp>; using FD = FpU<BN254_Fp_U>; using Fr = Fp<BN254_Fr>; static constexpr int BITS = 254; static constexpr int ID = 2;
+  static constexpr CurveTuning TUNE = {
+      /*acc_ns*/ 0.0685,
+      /*red_ns*/ 0.12,
+      /*narrow_prio_log2n*/ 19,
+      /*glv_log2n*/ 0,
+      /*glv_max_log2n*/ 0,
+      /*whole_tail_log2n*/ 21,
+      /*accum_handover*/ 16,
+      /*accum_handover_log2n*/ 20};
+};
+struct Bn254G2 { using F = Fp2<Fp<BN254_Fp>>; using FD = F; using Fr = Fp<BN254_Fr>; static constexpr int BITS = 254; static constexpr int ID = 3;
+  static constexpr CurveTuning TUNE = {
+      /*acc_ns*/ 0.5,
+      /*red_ns*/ 1.2,
+      /*narrow_prio_log2n*/ 0,
+      /*glv_log2n*/ 0,
+      /*glv_max_log2n*/ 0,
+      /*whole_tail_log2n*/ 0,
+      /*accum_handover*/ 0,
+      /*accum_handover_log2n*/ 0};
+};
+struct PallasEc { using F = Fp<Pallas_Fp>; using FD = FpU<Pallas_Fp_U>; using Fr = Fp<Vesta_Fp>; static constexpr int BITS = 255; static constexpr int ID = 4;
+  static constexpr CurveTuning TUNE = {
+      /*acc_ns*/ 0.056,
+      /*red_ns*/ 0.10,
+      /*narrow_prio_log2n*/ 0,
+      /*glv_log2n*/ 0,
+      /*glv_max_log2n*/ 0,
+      /*whole_tail_log2n*/ 21,
+      /*accum_handover*/ 16,
+      /*accum_handover_log2n*/ 20};
+};
+struct VestaEc { using F = Fp<Vesta_Fp>; using FD = FpU<Vesta_Fp_U>; using Fr = Fp<Pallas_Fp>; static constexpr int BITS = 255; static constexpr int ID = 5;
+  static constexpr CurveTuning TUNE = {
+      /*acc_ns*/ 0.056,
+      /*red_ns*/ 0.10,
+      /*narrow_prio_log2n*/ 0,
+      /*glv_log2n*/ 0,
+      /*glv_max_log2n*/ 0,
+      /*whole_tail_log2n*/ 21,
+      /*accum_handover*/ 16,
+      /*accum_handover_log2n*/ 20};
+};
 // Banderwagon: twisted Edwards (a = -5) over the BLS12-381 scalar field; ec.h selects the extended-coordinate law by the field type.
 // The device field is the saturated Fp (FD = F, as for BN254 G2): no carry-free set for this modulus yet, so there is no record
-// conversion and the mixed addition computes x*y itself (10M).  ACC_NS / RED_NS: ESTIMATES, not tuned -- about twice Pallas's figures
+// conversion and the mixed addition computes x*y itself (10M).  acc_ns / red_ns: ESTIMATES, not tuned -- about twice Pallas's figures
 // (saturated field, 10M against 8M+2S); DESIGN.md section 10 has the measured k_accum.
-struct Banderwagon { using F = Fp<Banderwagon_Fp>; using FD = F; using Fr = Fp<Banderwagon_Fr>; static constexpr int BITS = 253; static constexpr int ID = 6; static constexpr double ACC_NS = 0.12, RED_NS = 0.20; static constexpr int NARROW_PRIO_LOG2N = 0; static constexpr int GLV_LOG2N = 0, GLV_MAX_LOG2N = 0; static constexpr int WHOLE_TAIL_LOG2N = 0; static constexpr int ACCUM_HANDOVER = 0, ACCUM_HANDOVER_LOG2N = 0; };
+struct Banderwagon { using F = Fp<Banderwagon_Fp>; using FD = F; using Fr = Fp<Banderwagon_Fr>; static constexpr int BITS = 253; static constexpr int ID = 6;
+  static constexpr CurveTuning TUNE = {
+      /*acc_ns*/ 0.12,
+      /*red_ns*/ 0.20,
+      /*narrow_prio_log2n*/ 0,
+      /*glv_log2n*/ 0,
+      /*glv_max_log2n*/ 0,
+      /*whole_tail_log2n*/ 0,
+      /*accum_handover*/ 0,
+      /*accum_handover_log2n*/ 0};
+};
 
 // ---------------------------------------------------------------------------------------------
 // Booth signed digits
@@ -291,7 +372,7 @@ struct AccumArgs {
   uint32_t* tkey;                // [W][G]
   uint32_t N, B, K, G;
   // device only: the wave runs at raised priority until this many iterations before the end of a full lane range (accum_body_xyzz), 0 = no
-  // priority instruction at all (Curve::ACCUM_HANDOVER, option "accum_handover")
+  // priority instruction at all (CurveTuning::accum_handover, option "accum_handover")
   uint32_t handover = 0;
 };
 

@@ -14,6 +14,7 @@
 
 #include "host_fp64.h"
 #include "msm_bodies.h"
+#include "msm_place.h"
 #include "msm_plan.h"
 
 namespace ctt {
@@ -283,16 +284,16 @@ struct MsmEngine {
   // points_arrive (submit_host, a slice copied by the submitting thread): the points of this slice are not on the device yet -- the
   // digits and the sort need the coefficients only, so they are enqueued first, the hook then copies the points (the thread sits in that
   // copy while the GPU sorts) and the conversion follows the sort instead of preceding it.
-  // front_side (submit(), small MSMs kept in flight): conversion, digits and sort on the backend's front stream, beside the previous MSM's
+  // pl.front_side (small MSMs kept in flight): conversion, digits and sort on the backend's front stream, beside the previous MSM's
   // head merge and first reduction pass (HipBackend::front_begin has the ordering argument)
-  Staged accumulate_pairs(int sl, const MsmPlan& p, const uint32_t* d_coefs, bool coef_is_fr, const Affine<F>* d_points_in,
+  Staged accumulate_pairs(int sl, const MsmPlan& p, const Placement& pl, const uint32_t* d_coefs, bool coef_is_fr, const Affine<F>* d_points_in,
                           const void* d_prepared, void* d_converted, XYZZ<FD>* d_buckets, bool into = false,
-                          const std::function<void()>* points_arrive = nullptr, bool front_side = false) {
+                          const std::function<void()>* points_arrive = nullptr) {
     const uint32_t n = p.n, W = p.W, B = p.B;
     SortArgs sa;
     Staged st;
     uint32_t* d_scal = stage1_workspace(sl, p, coef_is_fr, sa, st);
-    if (front_side) bk.front_begin();
+    if (pl.front_side) bk.front_begin();
     bk.stage_begin(sl, ST_DIGITS);
     sa.scalars = d_coefs;
     if (coef_is_fr) {
@@ -329,30 +330,21 @@ struct MsmEngine {
       (void)accum_points(d_points_in, d_prepared, d_converted, n, true);   // (the conversion is timed with the sort in this form)
     }
     bk.stage_end(sl, ST_SORT);
-    if (front_side) bk.front_end();     // the accumulation below (main stream) waits for the sort
+    if (pl.front_side) bk.front_end();     // the accumulation below (main stream) waits for the sort
 
-    // The previous MSM's tail (narrow reduction passes + result copy on the backend's second stream) has had this MSM's
-    // conversion and sort to run underneath; the accumulation must not start before it is done: k_accum takes every
-    // wave slot of the chip for its whole duration, and a tail kernel enqueued behind it would wait it out (measured on
-    // a slower box: reduce span 2.4 ms, the pipeline slower than the serial order).  Worst case this is the serial order.
+    // The previous MSM's tail has had this MSM's conversion and sort to run underneath; whether the accumulation waits for all of it or
+    // only for its wide passes is the placement's (msm_place.h place_accum).
     // (the sort above has left this slot's bucket set with its empty buckets neutral -- SortArgs::zero_base -- and the previous MSM
     // runs on the other slot's set)
     // (into: a later slice of a host-pointer MSM continues the sums of the earlier slices, accum_body_xyzz)
-    // When the accumulate grid leaves wave slots free (submit() sees to that for a caller that keeps MSMs in flight: 1/16 of the
-    // slots up to 2^17 pairs, 1/64 of them while that costs less than half the wait), the previous tail's narrow passes run next to it, and the wait moves to the
-    // start of this MSM's reduction (reduce_buckets), the first kernel that writes what the tail still reads.
-    const uint64_t accum_waves = (uint64_t)W * ((p.G + 63u) / 64u);
-    // (partitioned chip, HipBackend::partitioned: the tail stream has compute units of its own -- nothing to wait for, no slots to leave)
-    // (Curve::WHOLE_TAIL_LOG2N: large MSMs of the curves whose accumulate kernel owns every register wait for the whole tail whatever the grid leaves free)
-    const bool whole_tail = C::WHOLE_TAIL_LOG2N > 0 && p.pairs() >= (1u << C::WHOLE_TAIL_LOG2N);
-    if (!bk.partitioned() && (whole_tail || accum_waves + tail_min_free_waves() > (uint64_t)opt.lanes / 64u)) bk.tail_wait();
+    if (pl.wait_whole_tail) bk.tail_wait();
     bk.wide_wait();   // (nothing to wait for unless the previous reduction put wide passes on the tail stream)
     bk.stage_begin(sl, ST_ACCUM);
     st.d_buckets = d_buckets;
     AccumArgs<FD> aa{sa.entries, st.d_bstart, d_points, record_stride(), d_buckets, st.d_heads, st.d_tails, st.d_hkey, st.d_tkey, p.nent, B, p.K, p.G};
-    aa.handover = accum_handover(p);
+    aa.handover = pl.handover;
     bk.template launch_accum<FD>(aa, W, into);
-    bk.accum_mark(front_side);          // (what the next small MSM's front stage waits for: the shared entry list and records are free again)
+    bk.accum_mark(pl.front_side);       // (what the next small MSM's front stage waits for: the shared entry list and records are free again)
     bk.stage_end(sl, ST_ACCUM);
     return st;
   }
@@ -397,51 +389,26 @@ struct MsmEngine {
   // kernel pays as well, and a launch spreads every level over the whole chip where a workgroup has 256 lanes; the waves of a
   // fused kernel also drift apart (different passes, different task kinds) and each then streams the addition's code through
   // the instruction cache on its own.  profiles/reduce_fused_vs_passes_r03.txt; the code is in the history (a64cd06).
-  void reduce_buckets(int sl, const MsmPlan& p, XYZZ<FD>* d_buckets) {
+  void reduce_buckets(int sl, const MsmPlan& p, const Placement& pl, XYZZ<FD>* d_buckets) {
     Slot& S = slots[sl];
     const uint32_t W = p.W, B = p.B;
-    const bool forked_early = bk.tail_forked();   // submit() forked in front of the head merge (early tail)
-    if (!forked_early) bk.tail_wait();   // (a no-op unless accumulate_pairs left the previous tail running: small MSMs)
+    if (!pl.early_tail()) bk.tail_wait();   // (a no-op unless accumulate_pairs left the previous tail running: small MSMs)
     bk.stage_begin(sl, ST_REDUCE);
     XYZZ<FD>* d_pyr = (XYZZ<FD>*)need(rA[0], (size_t)W * B * sizeof(XYZZ<FD>));
     XYZZ<FD>* d_q = (XYZZ<FD>*)need(rA[1], (size_t)W * (B / 2 + 1) * sizeof(XYZZ<FD>));
     XYZZ<FD>* d_out = (XYZZ<FD>*)need(rP[0], (size_t)W * p.c * sizeof(XYZZ<FD>));
     XYZZ<FD>* d_wsum = (XYZZ<FD>*)need(rP[1], (size_t)W * p.ngrp * sizeof(XYZZ<FD>));
-    // The narrow passes at the end, the bit Horner and the result copy move to the backend's tail stream: they are
-    // latency-bound and the next MSM's conversion and sort fit underneath them (the tail_wait() before the accumulation also
-    // orders the previous tail before this MSM's first write to the pyramid buffers).
-    // (only for a caller that keeps MSMs in flight -- the other slot is busy: a lone blocking call would pay the fork's
-    // event record and wait, ~15 us, for nothing)
-    const bool pipelining = other_busy(sl);
-    // wide_early: every pass but the first goes to the tail stream, the wide ones next to the following MSM's conversion and sort
-    // (VALU-bound additions beside memory-bound kernels); that MSM's accumulation waits for the end of the WIDE passes only
-    // (wide_mark / wide_wait) -- the narrow rest runs beside it in the wave slots its grid leaves free.
-    // Same box, ms per MSM with / without (profiles/wide_passes_on_tail_r03.txt): BLS12-381 G1 2^20 2.92 / 2.97, 2^18 0.965 / 0.977, 2^22 10.70 /
-    // 10.75; no difference for the other curves -- the kernels do slow each other down (round 2 measured the sort 0.19 -> 0.23 ms
-    // under wide passes), a quarter of the overlap is what remains.
-    static const bool wide_early = env_int("CTT_HIP_MSM_WIDE_EARLY", 1) != 0;
-    bool forked = forked_early, marked = forked_early && bk.partitioned();   // (partitioned: submit() marked behind the merge)
-    const bool first_pass_on_tail = opt.pyr0_tail == 1 && p.pairs() <= (1u << 17) && !p.merged;   // (MsmOptions::pyr0_tail: measured, off)
-    bk.narrow_priority(C::NARROW_PRIO_LOG2N > 0 && p.pairs() <= (1u << C::NARROW_PRIO_LOG2N));
-    for (int pass = 0; pass <= p.c - 2; pass++) {
+    // The narrow passes at the end, the bit Horner and the result copy move to the backend's tail stream, the wide passes too where the placement
+    // says so (msm_place.h place_reduction; the tail_wait() before the accumulation also orders the previous tail before this MSM's first write to
+    // the pyramid buffers).
+    bk.narrow_priority(pl.narrow_priority);
+    for (int pass = 0; pass <= p.c - 1; pass++) {   // (pass c - 1: behind the last one)
+      if (pass == pl.tail_from) bk.tail_begin();
+      if (pass == pl.wide_mark_at) bk.wide_mark();
+      if (pass == p.c - 1) break;
       PyrArgs<FD> pa{d_buckets, d_pyr, d_q, d_out, B, p.c, pass, 1u};
-      const uint32_t ntasks = pyr_pass_tasks(B, p.c, pass);
-      const bool narrow = bk.pyr_goes_to_tail(ntasks, W);
-      if (pipelining && !forked && (pass > 0 || first_pass_on_tail) && (narrow || wide_early)) {
-        bk.tail_begin();
-        forked = true;
-      }
-      if (forked && !marked && narrow) {
-        bk.wide_mark();
-        marked = true;
-      }
-      bk.template launch_pyr<FD>(pa, W, ntasks);
+      bk.template launch_pyr<FD>(pa, W, pyr_pass_tasks(B, p.c, pass));
     }
-    if (pipelining && !forked) {
-      bk.tail_begin();
-      forked = true;
-    }
-    if (forked && !marked) bk.wide_mark();
     bk.template launch_window_groups<FD>(d_out, d_wsum, W, p.c, p.h, p.ngrp);
     bk.stage_end(sl, ST_REDUCE);
 
@@ -453,29 +420,14 @@ struct MsmEngine {
     }
     bk.d2h_async(sl, S.hraw, d_wsum, bytes);
     bk.stage_end(sl, ST_TOTAL);
-    if (forked) bk.tail_end();
+    if (pl.tail_from != Placement::NEVER) bk.tail_end();
   }
 
-  // Wave slots the accumulate grid must leave free for the previous MSM's tail to run beside it (fewer: the accumulation waits
-  // for that tail first), and how much of an accumulation submit() may spend on leaving slots free on purpose for an MSM kept
-  // in flight ...
-  static uint32_t tail_min_free_waves() {
-    static const uint32_t v = (uint32_t)env_int("CTT_HIP_MSM_TAIL_MIN_FREE", 16);
-    return v;
-  }
-  // ... as a fraction of the wait it removes, which is about one tenth of a millisecond for BLS12-381 G1 and scales with the
-  // curve's addition time (the tail is a chain of dependent additions)
-  static double tail_free_cost_ratio() {
-    static const double v = env_double("CTT_HIP_MSM_TAIL_FREE_RATIO", 0.5);
-    return v;
-  }
-
-  // Drop distance of the accumulate kernel's priority hand-over for this plan (hip_backend.h k_accum), 0 = none.  By the curve's measurement
-  // (msm_bodies.h ACCUM_HANDOVER, ACCUM_HANDOVER_LOG2N) unless the option names a distance: K / 8, and not below the curve's floor.
-  uint32_t accum_handover(const MsmPlan& p) const {
-    if (opt.accum_handover >= 2) return (uint32_t)opt.accum_handover;
-    if (opt.accum_handover != 1 || C::ACCUM_HANDOVER == 0 || p.pairs() < (1u << C::ACCUM_HANDOVER_LOG2N)) return 0u;
-    return p.K / 8u > (uint32_t)C::ACCUM_HANDOVER ? p.K / 8u : (uint32_t)C::ACCUM_HANDOVER;
+  // what the placement decisions look at, for the MSM in slot sl (msm_place.h); the cost model's figures are the curve's
+  PlaceInputs place_inputs(int sl, const void* d_prepared, int table_c) {
+    opt.acc_ns = C::TUNE.acc_ns;
+    opt.red_ns = C::TUNE.red_ns;
+    return PlaceInputs{opt, C::TUNE, other_busy(sl), bk.partitioned(), d_prepared != nullptr, table_c};
   }
 
   int claim_slot(uint32_t n) {
@@ -496,108 +448,38 @@ struct MsmEngine {
              const void* d_prepared = nullptr, int table_c = 0, uint32_t table_n = 0) {
     const int sl = claim_slot(n);
     if (sl < 0 || n == 0) return sl;
-    opt.acc_ns = C::ACC_NS;
-    opt.red_ns = C::RED_NS;
+    // where and when everything below runs: decided here, once (msm_place.h has the decisions and the measurements behind them)
+    const PlaceInputs pin = place_inputs(sl, d_prepared, table_c);
+    Placement pl = place_lanes(pin, n, C::BITS, GlvOf<C>::BITS, kGlv);
+    const uint32_t pn = pl.glv ? 2u * n : n;                    // entries per bucket set and bits of a scalar the plan is made for
     MsmOptions po = opt;
-    // The endomorphism split (msm_bodies.h bls12_381_glv_split): 2n entries of 127 bits in place of n of 255 -- the same accumulations in half the
-    // bucket sets.  Device-resident points without cached records or a table, at the curve's sizes (GLV_LOG2N .. GLV_MAX_LOG2N) or as the option says.
-    bool glv = false;
-    if constexpr (kGlv) {
-      glv = !d_prepared && table_c <= 0 && n <= (1u << 30) && opt.glv != 2 && (opt.glv == 1 || (C::GLV_LOG2N > 0 && n >= (1u << C::GLV_LOG2N) && n <= (1u << C::GLV_MAX_LOG2N)));
-    }
-    const uint32_t pn = glv ? 2u * n : n;                    // entries per bucket set and bits of a scalar the plan is made for
-    const int pbits = glv ? GlvOf<C>::BITS : C::BITS;
-    // A caller that keeps MSMs in flight gets the tail of the previous MSM (reduction passes behind the first, bit Horner, result
-    // copy: latency-bound, a few dozen waves at a time) run BESIDE this accumulation when the accumulate grid leaves wave slots free
-    // (accumulate_pairs); it pays to leave them free on purpose.  Up to 2^17 pairs: 1/16 of the lanes.  (Round 2 took 5/32 -- BLS12-381
-    // G1 2^17, ms per MSM with two in flight: 0.69 with 17 % of the slots free, 0.80 with 5 %; since the larger sizes stopped waiting
-    // for the tail too, 1/16 measures level or better: 2^17 0.742 against 0.759 ms with 5/32, G2 2^16 1.048 against 1.074.)
-    // (the window size is chosen for the whole chip first: fewer lanes must only lengthen K)
-    if (bk.partitioned()) {
-      // (the tail runs on compute units the accumulate grid never sees: opt.lanes counts the main stream's CUs only)
-    } else if (other_busy(sl) && n <= (1u << 17) && opt.K <= 0 && table_c <= 0) {
-      if (po.c <= 0) po.c = choose_window_bits(pn, pbits, opt.lanes, opt.acc_ns, opt.red_ns);
-      static const uint32_t free32 = (uint32_t)env_int("CTT_HIP_MSM_SMALL_FREE_32NDS", 2);
-      po.lanes = (uint32_t)((uint64_t)opt.lanes * (32u - (free32 < 31u ? free32 : 31u)) / 32u);
-    } else if (other_busy(sl) && opt.K <= 0 && table_c <= 0 && opt.lanes >= 64u * 1024u && opt.acc_ns >= 0.1) {
-      // Larger ones: the accumulation used to wait for the previous tail -- ten dependent narrow passes, the bit Horner and the result
-      // copy, ~0.25 ms after the last wide pass, 0.1 ms longer than this MSM's sort (rocprof timeline, BLS12-381 2^20: the sort ends
-      // at 177 us, the accumulation started at 281).  With 1/64 of the wave slots left free (32 of 2048; K 128 -> 131 at 2^20) the
-      // tail finishes beside the accumulation instead.  Same box, ms per MSM with / without: BLS12-381 G1 2^19 1.72 / 1.82,
-      // 2^20 2.92 / 2.98, 2^21 5.54 / 5.59, 2^22 10.60 / 10.47; G2 2^18 2.92 / 3.13, 2^20 9.50 / 9.46 -- it pays while that share of the
-      // accumulation is well below the wait (profiles/sweep_free_wave_slots_r03.txt).  Not for the 254/255-bit G1 fields (acc_ns < 0.1):
-      // their additions are twice as fast, their tail ends before their sort does, and the free slots only cost (Pallas 2^20 1.455 / 1.433).
-      if (po.c <= 0) po.c = choose_window_bits(pn, pbits, opt.lanes, opt.acc_ns, opt.red_ns);
-      int Wc;
-      window_layout(pbits, po.c, &Wc);
-      // 32 slots at least: a narrow pass is up to 64 waves, and a G2 wave needs a SIMD to itself (16 free slots of its 1024
-      // measured no gain, 32 did: 3.13 -> 2.92 ms at 2^18)
-      const uint32_t nslots = opt.lanes / 64u, free_slots = nslots / 64u > 32u ? nslots / 64u : 32u;
-      const double cost_ms = (double)Wc * pn * opt.acc_ns * 1e-6 * free_slots / nslots, wait_ms = 0.1 * opt.acc_ns / 0.142;
-      if (cost_ms <= tail_free_cost_ratio() * wait_ms) po.lanes = opt.lanes - 64u * free_slots;
-    }
-    MsmPlan planned = table_c > 0 ? make_table_plan(n, C::BITS, table_c, table_n, po) : make_plan(pn, pbits, po);
-    planned.glv = glv ? 1u : 0u;
+    po.c = pl.c;
+    po.lanes = pl.lanes;
+    MsmPlan planned = table_c > 0 ? make_table_plan(n, C::BITS, table_c, table_n, po) : make_plan(pn, pl.glv ? GlvOf<C>::BITS : C::BITS, po);
+    planned.glv = pl.glv ? 1u : 0u;
     const MsmPlan p = planned;
     slots[sl].plan = p;
     last_plan = p;
+    place_accum(pl, pin, p, /*device_resident=*/true);
+    place_reduction(pl, pin, p, /*may_start_early=*/true, [&](uint32_t ntasks, uint32_t W) { return bk.pyr_goes_to_tail(ntasks, W); });
     try {
       bk.stage_begin(sl, ST_TOTAL);
       void* d_converted = (kConvert && !d_prepared) ? need(cpoints, (size_t)pn * record_stride()) : nullptr;
       XYZZ<FD>* d_buckets = (XYZZ<FD>*)need(bucketsS[sl], (size_t)p.W * p.B * sizeof(XYZZ<FD>));
-      // Round 5 experiment (option front_side = 1; off by default: front_side_applies has the measurements): conversion and sort of a small MSM
-      // submitted while another is in flight on the front stream, beside that MSM's head merge and first reduction pass.
-      const bool front_side = front_side_applies(p);
-      const Staged st = accumulate_pairs(sl, p, d_coefs, coef_is_fr, d_points_in, d_prepared, d_converted, d_buckets, /*into=*/false, nullptr, front_side);
-      // Early tail (round 4): a caller that keeps large MSMs in flight gets the head merge and EVERY reduction pass of this MSM on the
-      // tail stream, so that the next MSM's conversion and sort -- memory-bound -- start right behind this accumulation instead of
-      // behind the merge and the widest pass (VALU-bound additions, 0.16 ms at 2^20).  What those stages read is per slot (bstartS,
-      // maxcountS, bucketsS); the next accumulation still waits for the end of the wide passes (wide_wait), so nothing of this tail
-      // competes with an accumulation for wave slots (which is what sank round 3's version for small MSMs, section 5 of DESIGN.md).
-      if (early_tail_applies(p)) {
+      const Staged st = accumulate_pairs(sl, p, pl, d_coefs, coef_is_fr, d_points_in, d_prepared, d_converted, d_buckets);
+      if (pl.early_tail()) {
         // (the previous tail ended long ago: it ran beside this accumulation.  Partitioned chip: it may still be crawling through its
         // wide passes on its few compute units -- the tail stream is in order, and nothing on the main stream touches what it uses)
-        if (!bk.partitioned()) bk.tail_wait();
+        if (!pin.partitioned) bk.tail_wait();
         bk.tail_begin();
       }
       merge_buckets(sl, p, st);
-      // Partitioned chip + early tail: the next accumulation shares the head / tail slots with this merge and nothing else with this
-      // tail -- it waits for the merge, not for the wide reduction passes (which run on the tail stream's own compute units)
-      if (bk.partitioned() && bk.tail_forked()) bk.merge_mark();
-      reduce_buckets(sl, p, d_buckets);
+      if (pl.wide_mark_at == Placement::AT_MERGE) bk.merge_mark();
+      reduce_buckets(sl, p, pl, d_buckets);
     } catch (const OutOfDeviceMemory&) {
       return release_slot(sl);
     }
     return sl;
-  }
-  // Only for a caller that is pipelining (the other slot is busy), from ~2^18 pairs on, and while the accumulation is shorter than ~6 ms.
-  // Measured on one box, ms per MSM with two in flight, off / on, three repetitions (profiles/early_tail_r04.txt): BLS12-381 G1 2^19
-  // 1.70 / 1.63, 2^20 2.90 / 2.81 (-3.1 %), BN254 2^20 1.62 / 1.58, 2^22 5.39 / 5.25, Pallas 2^20 1.46 / 1.40 (-3.9 %), 2^18 1.011 / 0.998;
-  // but BLS12-381 G1 2^22 10.5 / 10.6 and G2 2^20 9.45 / 9.49: with a 8-10 ms accumulation the 0.16 ms are 1.5 % at best and the sort
-  // (0.5 ms at 2^22) running beside the widest pass loses more than the overlap gives.
-  bool front_side_applies(const MsmPlan& p) const {
-    static const int mode = env_int("CTT_HIP_MSM_FRONT", 1);   // 0 off, 1 automatic, 2 whenever pipelining
-    if (mode == 0 || opt.front_side == 2) return false;
-    if (busy_count() < 2) return false;    // a lone blocking call has nothing to run beside
-    if (mode >= 2 || opt.front_side == 1) return true;
-    // Measured and NOT adopted (profiles/front_stream_small_msm_r05.txt, same box, ms per MSM with two in flight, main stream only / front stream):
-    // BLS12-381 G1 2^12 0.278 / 0.287, 2^14 0.388-0.393 / 0.383-0.386, 2^16 0.470 / 0.494, 2^17 0.637 / 0.664, G2 2^16 1.077 / 1.227.  The overlap
-    // is real (the sort leaves the main stream's chain), but with a second hardware queue active the dependent kernels of BOTH chains start later
-    // (round 3 saw the same with two engine lanes: 50-70 us between dependent launches).  What the experiment did find: a process has FOUR hardware
-    // queues (GPU_MAX_HW_QUEUES); with the front stream as a FIFTH stream of the context (null, main, tail, copy, front) two streams shared a queue
-    // and every small pipelined MSM lost 8 % (2^16: 0.52 -> 0.56 ms) without a single kernel on the new stream -- the front stage therefore
-    // runs on the copy stream (HipBackend::init), and nothing in the library may add a stream lightly.
-    (void)p;
-    return false;
-  }
-  bool early_tail_applies(const MsmPlan& p) const {
-    static const int mode = env_int("CTT_HIP_MSM_EARLY_TAIL", 1);   // 0 off, 1 automatic, 2 whenever pipelining
-    if (mode == 0 || opt.early_tail == 0) return false;
-    const bool pipelining = busy_count() >= 2;
-    if (!pipelining) return false;
-    if (mode >= 2 || opt.early_tail >= 2) return true;
-    const double additions = (double)p.nent * (double)p.W;
-    return additions >= (double)(1u << 22) && additions * opt.acc_ns < 6.0e6;
   }
   // a submit that ran out of device memory: what it enqueued so far runs to its end on buffers that stay valid (a buffer is
   // only ever freed by need(), and hipFree waits for the device); the slot is free again.  Returns the error value -2.
@@ -618,7 +500,7 @@ struct MsmEngine {
   // The slices of a host-pointer call (msm_plan.h host_slices has the model) with this curve's figures: windows x the accumulate time per
   // pair on the GPU; 32 bytes of scalar and the point cross the link (scalars_only: the bases are cached on the device)
   static std::vector<uint32_t> host_slices(uint32_t n, int want, bool scalars_only = false) {
-    return ctt::host_slices(n, want, (double)((C::BITS + 16) / 16) * C::ACC_NS * 1.09, 32 + (scalars_only ? 0 : sizeof(Affine<F>)));
+    return ctt::host_slices(n, want, (double)((C::BITS + 16) / 16) * C::TUNE.acc_ns * 1.09, 32 + (scalars_only ? 0 : sizeof(Affine<F>)));
   }
   // d_prepared (with table_c / table_n for a window table): the bases are cached on the device (prepare_bases / prepare_table), only the
   // coefficients are host-resident -- the ZAL msm_with_cached_base shape with host scalars; h_points and d_stage_points are not used.
@@ -633,8 +515,9 @@ struct MsmEngine {
     const uint32_t nch = (uint32_t)bound.size() - 1;
     uint32_t largest = 0;
     for (uint32_t i = 0; i < nch; i++) largest = bound[i + 1] - bound[i] > largest ? bound[i + 1] - bound[i] : largest;
-    opt.acc_ns = C::ACC_NS;
-    opt.red_ns = C::RED_NS;
+    const PlaceInputs pin = place_inputs(sl, d_prepared, table_c);
+    Placement pl;
+    place_host(pl, pin, nch, BK::THREADED_UPLOAD);
     MsmOptions o = opt;
     if (o.c <= 0) o.c = choose_window_bits(n, C::BITS, o.lanes, o.acc_ns, o.red_ns);  // one window size for the whole MSM
     try {
@@ -658,9 +541,7 @@ struct MsmEngine {
       if (!d_prepared)
         bk.h2d((Affine<F>*)d_stage_points + start, (const char*)h_points + (size_t)start * sizeof(Affine<F>), (size_t)cnt * sizeof(Affine<F>));
     };
-    // Several slices: a thread of its own issues the copies back to back (HipBackend::h2d_slice_done has the reason), this one
-    // enqueues slice i's kernels as soon as slice i has been handed to the link.
-    bool threaded = BK::THREADED_UPLOAD && nch > 2;   // (two slices: one gap of ~0.1 ms against a thread start of about as much -- measured: 2^18 1.85 ms without, 1.93 with)
+    bool threaded = pl.threaded;   // (msm_place.h place_host)
     std::atomic<uint32_t> uploaded{0}, coefs_up{0};
     std::atomic<bool> upload_failed{false};   // a HIP call failed on the uploader thread: reported by THIS thread (the one an entry point's error channel belongs to)
     std::thread uploader;
@@ -710,11 +591,7 @@ struct MsmEngine {
         }
         if (upload_failed.load(std::memory_order_acquire)) bk.uploader_failed();   // (throws to the entry point's boundary, or aborts where there is none)
       };
-      // The first slice starts on its coefficients: the digits and the sort need nothing else, and they run while the slice's points
-      // cross the link (accumulate_pairs, points_arrive).  Later slices wait for both copies at once (their sort queues behind the
-      // previous accumulation anyway, and an event between their copies would hold the second one back: see the uploader).
-      static const bool late_env = env_int("CTT_HIP_MSM_LATE_POINTS", 1) != 0;   // (0: both copies first)
-      const bool late_points = late_env && i == 0 && !d_prepared;
+      const bool late_points = pl.late_points && i == 0;   // (msm_place.h place_host)
       if (threaded) {
         if (late_points) {
           await(coefs_up, i);
@@ -754,7 +631,8 @@ struct MsmEngine {
       void* d_conv = (kConvert && !d_prepared) ? (void*)((char*)d_conv_all + (size_t)start * record_stride()) : nullptr;
       // (cached bases: the slice's records -- or, in a window table, its column of every row block: row w * table_n + j -- start `start` records in)
       const void* d_prep = d_prepared ? (const void*)((const char*)d_prepared + (size_t)start * record_stride()) : nullptr;
-      st_prev = accumulate_pairs(sl, p, d_c, coef_is_fr, d_prepared ? nullptr : d_p, d_prep, d_conv, d_sets, /*into=*/i > 0,
+      place_accum(pl, pin, p, /*device_resident=*/false);
+      st_prev = accumulate_pairs(sl, p, pl, d_c, coef_is_fr, d_prepared ? nullptr : d_p, d_prep, d_conv, d_sets, /*into=*/i > 0,
                                  late_points ? &points_arrive : nullptr);
       p_prev = p;
       plast = p;
@@ -764,7 +642,8 @@ struct MsmEngine {
     slots[sl].plan = plast;
     last_plan = plast;
     last_chunks = nch;
-    reduce_buckets(sl, plast, d_sets);
+    place_reduction(pl, pin, plast, /*may_start_early=*/false, [&](uint32_t ntasks, uint32_t W) { return bk.pyr_goes_to_tail(ntasks, W); });
+    reduce_buckets(sl, plast, pl, d_sets);
     } catch (const OutOfDeviceMemory&) {
       return release_slot(sl);
     }

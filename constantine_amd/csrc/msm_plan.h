@@ -11,7 +11,7 @@
 
 namespace ctt {
 
-// An environment knob: callers keep the value in a function-local static, so each is read once per process, before its first use.
+// An environment knob: callers keep the value in a static, so each is read once per process, before its first use.
 static inline int env_int(const char* name, int dflt) { const char* s = getenv(name); return s ? atoi(s) : dflt; }
 static inline double env_double(const char* name, double dflt) { const char* s = getenv(name); return s ? atof(s) : dflt; }
 
@@ -72,11 +72,11 @@ struct MsmOptions {
   // BLS12-381 G1 2^16 0.466-0.473 / 0.480, 2^17 0.654-0.657 / 0.676-0.680, BN254 2^16 0.345 / 0.350 -- the fork's event pair costs what the
   // 25 us of overlap give (gpurun_out/r5i)
   int pyr0_tail = 0;
-  // the endomorphism split of a device-resident MSM (curves that have one: msm_bodies.h GlvOf): 0 = at the curve's sizes (GLV_LOG2N .. GLV_MAX_LOG2N),
+  // the endomorphism split of a device-resident MSM (curves that have one: msm_bodies.h GlvOf): 0 = at the curve's sizes (CurveTuning::glv_log2n .. glv_max_log2n),
   // 1 = at every size, 2 = never.  Option "glv", $CTT_HIP_MSM_GLV.
   int glv = 0;
   // the priority hand-over of the accumulate kernel (hip_backend.h k_accum): 0 = off (no priority instruction runs), 1 = the curve's drop distance at the
-  // curve's sizes (msm_bodies.h Curve::ACCUM_HANDOVER, ACCUM_HANDOVER_LOG2N; msm_pipeline.h accum_handover), n >= 2 = this drop distance at every size.  Option "accum_handover", $CTT_HIP_MSM_ACCUM_HANDOVER.
+  // curve's sizes (msm_bodies.h CurveTuning::accum_handover, accum_handover_log2n; msm_place.h place_accum), n >= 2 = this drop distance at every size.  Option "accum_handover", $CTT_HIP_MSM_ACCUM_HANDOVER.
   int accum_handover = 1;
 };
 

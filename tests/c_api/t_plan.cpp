@@ -62,8 +62,8 @@ static int dump() {
             }
       const int ctab = choose_table_window_bits(n, bits);
       printf("choose bits=%d n=%u: g1 %d %d %d g2 %d bn %d table %d\n", bits, n, choose_window_bits(n, bits, 4096), choose_window_bits(n, bits, 131072),
-             choose_window_bits(n, bits, 196608), choose_window_bits(n, bits, 196608, Bls12381G2::ACC_NS, Bls12381G2::RED_NS),
-             choose_window_bits(n, bits, 196608, Bn254G1::ACC_NS, Bn254G1::RED_NS), ctab);
+             choose_window_bits(n, bits, 196608), choose_window_bits(n, bits, 196608, Bls12381G2::TUNE.acc_ns, Bls12381G2::TUNE.red_ns),
+             choose_window_bits(n, bits, 196608, Bn254G1::TUNE.acc_ns, Bn254G1::TUNE.red_ns), ctab);
       for (int c : {0, 4, 8, 13, 16, 20, 22}) {
         const int ct = c ? c : ctab;
         if (ct <= 0 || !table_plan_fits(n, bits, ct)) continue;

@@ -105,8 +105,8 @@ def test_default_plan(name, inputs, expected, eng):
 
 @pytest.mark.parametrize("name, log2n", [(BLS, 19), (BN, 20)])
 def test_curve_default_at_its_size_bound(name, log2n, eng, torch_cuda):
-    """The smallest size at which option 1 switches the hand-over on by itself (msm_bodies.h ACCUM_HANDOVER_LOG2N; every other case of this file
-    is below it, where 1 resolves to off): the distance is then max(floor, K / 8) of the plan's own K (msm_pipeline.h accum_handover).  Off, the
+    """The smallest size at which option 1 switches the hand-over on by itself (msm_bodies.h accum_handover_log2n; every other case of this file
+    is below it, where 1 resolves to off): the distance is then max(floor, K / 8) of the plan's own K (msm_place.h place_accum).  Off, the
     default, and the explicit distances K / 8 and K - 1 (the drop point at the first iteration) give the same bytes, the oracle's."""
     n = 1 << log2n
     curve = po.CURVES[name]

@@ -134,12 +134,12 @@ def test_three_in_flight_alternating_inputs(cases, eng, torch_cuda):
 
 
 # the sizes at which a device-resident MSM without cached bases takes the split by default: 2^GLV_LOG2N .. 2^GLV_MAX_LOG2N pairs
-# (csrc/msm_bodies.h Bls12381G1::GLV_LOG2N, GLV_MAX_LOG2N)
+# (csrc/msm_bodies.h Bls12381G1::TUNE: glv_log2n, glv_max_log2n)
 GLV_LOG2N, GLV_MAX_LOG2N = 17, 21
 
 
 def test_default_follows_the_curve_sizes(cases, torch_cuda):
-    """option "glv" = 0: the split runs at the curve's sizes (msm_bodies.h GLV_LOG2N .. GLV_MAX_LOG2N; 0 = never) and never on the
+    """option "glv" = 0: the split runs at the curve's sizes (msm_bodies.h glv_log2n .. glv_max_log2n; 0 = never) and never on the
     other curves; the result is the same either way"""
     from constantine_amd import DeviceMsm
     ds, dp, sc, expect = cases[4096]
