@@ -11,6 +11,7 @@ Only what the MSM hot path needs lives here:
             process driving several GPUs, is ctt_hip_msm_set_devices / $CTT_HIP_DEVICES (msm.set_devices)
   synth.py  synthetic benchmark inputs (seeded scalars)
   verkle.py  batched Verkle commitments over a fixed Banderwagon basis: VerkleCrs.commit, batchMapToScalarField, serializeBatch_vartime
+  fixed.py  batched fixed-base MSM over BLS12-381 G1 / BN254 G1 (FixedBaseMsm; include/ctt_msm_hip_fixed.h -> libctt_msm_hip_fixed.so)
   ntt.py    batched NTT over a curve's scalar field (NttPlan); the EIP-7594 cells and cell proofs of kzg.py run on it
   kzg.py, evm.py  ctypes callers of the reference's KZG / EIP-2537 MSM-precompile C symbols (csrc/protocols.hip: host side in C++)
 """
@@ -30,3 +31,4 @@ from .msm import (  # noqa: F401
     set_shard_min,
 )
 from .verkle import VerkleCrs, batchMapToScalarField, serializeBatch_vartime  # noqa: F401
+from .fixed import FixedBaseMsm, FixedMsmRefused  # noqa: F401

@@ -1,16 +1,18 @@
 """ctypes loader for libctt_msm_hip.so. The product path has no fallback: a missing library is an error.
 
-The prototypes of both libraries are the two tables below, name -> (restype, argtypes); tests/test_abi_symbols.py derives the same
-from the C headers and compares."""
+The prototypes of the libraries are the tables below, name -> (restype, argtypes); tests/test_abi_symbols.py and
+tests/test_fixed_abi.py derive the same from the C headers and compare."""
 import ctypes
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CTT_MSM_HIP_LIB") or os.path.join(HERE, "libctt_msm_hip.so")
 BW_LIB_PATH = os.path.join(HERE, "libctt_msm_hip_banderwagon.so")
+FIXED_LIB_PATH = os.path.join(HERE, "libctt_msm_hip_fixed.so")
 
 _lib = None
 _bw_lib = None
+_fixed_lib = None
 ABI_VERSION = 11  # ctt_hip_msm_abi_version() of the library this package was written against
 GPU_UNAVAILABLE = 0xF0   # CTT_HIP_STATUS_GPU_UNAVAILABLE: what a protocol symbol returns when the GPU cannot serve the call
 
@@ -22,6 +24,7 @@ class HipLibraryMissing(RuntimeError):
 vp, sz, i32, u32, u64, cstr = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_char_p
 u8 = ctypes.c_uint8                                  # the reference's status enums are __attribute__((__packed__)): one byte
 pvp, pi32 = ctypes.POINTER(vp), ctypes.POINTER(i32)  # out-handles and int arrays the callers pass with byref / as ctypes arrays
+psz, pf32 = ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_float)
 
 
 def _msm_families():
@@ -123,6 +126,17 @@ for _coef in ("big", "fr"):
     BW_PROTOTYPES[f"ctt_hip_msm_banderwagon_ec_prj_{_coef}"] = (i32, [vp, vp, vp, sz])
 
 
+# include/ctt_msm_hip_fixed.h: the batched fixed-base MSM over BLS12-381 G1 and BN254 G1 (a library with kernels of its own)
+FIXED_PROTOTYPES = {
+    "ctt_hip_fixed_bases_create": (vp, [i32, i32, vp, sz, i32]),
+    "ctt_hip_fixed_bases_destroy": (None, [vp]),
+    "ctt_hip_fixed_bases_info": (i32, [vp, psz]),
+    "ctt_hip_fixed_msm_batch": (i32, [vp, i32, vp, sz, vp, i32]),
+    "ctt_hip_fixed_last_timings": (i32, [vp, pf32]),
+    "ctt_hip_fixed_last_error": (i32, []),
+}
+
+
 def exported_symbols():
     """Every symbol include/ctt_msm_hip.h declares."""
     return list(PROTOTYPES)
@@ -183,6 +197,17 @@ def banderwagon_lib():
             raise HipLibraryMissing(f"{BW_LIB_PATH} not found: build it with make -C constantine_amd/csrc")
         _bw_lib = _load(BW_LIB_PATH, BW_PROTOTYPES, "ctt_msm_hip_banderwagon.h")
     return _bw_lib
+
+
+def fixed_lib():
+    """libctt_msm_hip_fixed.so (include/ctt_msm_hip_fixed.h): the batched fixed-base MSM.  It does not need lib(), but shares its HIP runtime."""
+    global _fixed_lib
+    if _fixed_lib is None:
+        if not os.path.exists(FIXED_LIB_PATH):
+            raise HipLibraryMissing(f"{FIXED_LIB_PATH} not found: build it with make -C constantine_amd/csrc")
+        _share_hip_runtime_with_torch()
+        _fixed_lib = _load(FIXED_LIB_PATH, FIXED_PROTOTYPES, "ctt_msm_hip_fixed.h")
+    return _fixed_lib
 
 
 def lib():

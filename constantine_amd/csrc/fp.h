@@ -22,6 +22,9 @@
 #include <hip/hip_runtime.h>
 #define CTT_HD __host__ __device__ __forceinline__
 #define CTT_HD_NOINLINE __host__ __device__ __attribute__((noinline))
+#elif defined(CTT_HOST_INLINE_BY_COMPILER)   // a CPU test harness of 12-word fields: forced inlining costs it minutes of compile time
+#define CTT_HD inline
+#define CTT_HD_NOINLINE __attribute__((noinline))
 #else
 #define CTT_HD inline __attribute__((always_inline))
 #define CTT_HD_NOINLINE __attribute__((noinline))

@@ -15,8 +15,10 @@
 //   EIP-7594 PeerDAS ctt_eth_kzg_compute_cells_and_kzg_proofs (include/constantine/protocols/ethereum_eip7594_peerdas.h) and the
 //                   cells alone (ctt_hip_eth_kzg_compute_cells): the blob's coefficients, the coset evaluations and the 128 cell
 //                   quotients' evaluations are transforms of ctt_hip_fr_ntt (ntt.hip), the quotients one kernel here
-//                   (k_cell_quotients), the proofs 128 MSMs over the context's cached Lagrange bases.  Recovery, the batch
-//                   verification (pairings) and the FK20 form are out of scope.  DESIGN.md section 13.
+//                   (k_cell_quotients), the proofs 128 MSMs over the context's Lagrange points: one pass of the batched fixed-base
+//                   MSM (fixed.h; its table is built at the first proof call), or -- CTT_HIP_CELL_PROOFS=loop, or no memory for the
+//                   table -- a loop over the cached bases.  Recovery, the batch verification (pairings) and the FK20 form are out
+//                   of scope.  DESIGN.md sections 13 and 14.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,6 +27,8 @@
 #include <system_error>
 #include <thread>
 
+#include "fixed.h"
+#include "fixed_bodies.h"   // (the range of window sizes)
 #include "hip_errors.h"
 #include "msm_pipeline.h"   // (OutOfDeviceMemory)
 #include "protocols_host.h"
@@ -89,6 +93,14 @@ struct ctt_eth_kzg_context_struct {
   void* d_cellq = nullptr;
   uint8_t coset_shift[32];      // omega_8192, canonical
   float cell_ms[7] = {0, 0, 0, 0, 0, 0, 0};   // the last cells call: parse + upload, INTT, coset NTT, quotients, batched NTT, MSM loop, compress + copy back
+  // the cell proofs as one batched fixed-base MSM (fixed.h): the Lagrange points in the order of `bases`, kept on the host until the
+  // table is built at the first proof call; $CTT_HIP_CELL_PROOFS=loop at creation keeps the loop over `bases`, and so does a table
+  // that could not be allocated.  $CTT_HIP_CELL_PROOFS_C overrides the window bits.
+  std::vector<uint8_t> lagrange_aff;
+  FixedTable* fixed = nullptr;
+  bool proofs_loop = false;
+  int proofs_c = 0;
+  float cell_path[2] = {0, 0};   // the last cells call: rows the table kernel served (128 or 0), ms it paid for building the table
 };
 
 namespace {
@@ -99,6 +111,8 @@ void kzg_context_release(ctt_eth_kzg_context_struct* c, bool with_hip) {
   for (void* d : {c->d_domain, c->d_poly, c->d_q, c->d_ck, c->d_coef, c->d_coset, c->d_cellq})
     if (d) (void)hipFree(d);
   if (c->ntt) ctt_hip_fr_ntt_plan_destroy(c->hip, c->ntt);
+  delete c->fixed;   // (before the MSM context: the table works on its stream)
+  c->fixed = nullptr;
   if (with_hip && c->hip) ctt_hip_msm_ctx_destroy(c->hip);
 }
 
@@ -137,6 +151,14 @@ int kzg_context_build(ctt_eth_kzg_context_struct** out, const uint8_t* srs, int 
   c->bases = table ? ctt_hip_msm_bases_create_table(c->hip, CTT_HIP_BLS12_381_G1, aff.data(), N_BLOB, 0, 0)
                    : ctt_hip_msm_bases_create(c->hip, CTT_HIP_BLS12_381_G1, aff.data(), N_BLOB, 0);
   if (!c->bases) return fail(GPU_UNAVAILABLE);
+  {
+    const char* mode = getenv("CTT_HIP_CELL_PROOFS");
+    const char* bits = getenv("CTT_HIP_CELL_PROOFS_C");
+    c->proofs_loop = mode && !strcmp(mode, "loop");
+    c->proofs_c = bits ? atoi(bits) : 0;
+    if (c->proofs_c < FX_MIN_WINDOW_BITS || c->proofs_c > FX_MAX_WINDOW_BITS) c->proofs_c = 0;   // not a window size: the default, never a refused call
+    if (!c->proofs_loop) c->lagrange_aff = std::move(aff);
+  }
   c->domain = domain_brp();
   try {
     DeviceScope device_scope(device);
@@ -210,6 +232,7 @@ int kzg_cells(ctt_eth_kzg_context_struct* c, uint8_t* cells, uint8_t* proofs, ui
   hipStream_t s = (hipStream_t)ctt_hip_msm_stream(c->hip);
   if (!s) return GPU_UNAVAILABLE;
   float ms[7] = {0, 0, 0, 0, 0, 0, 0};
+  float path[2] = {0, 0};
   clk::time_point t0 = clk::now();
   PROT_HIP_CHECK(hipMemcpyAsync(c->d_poly, poly_le, (size_t)N_BLOB * 32, hipMemcpyHostToDevice, s));
   PROT_HIP_CHECK(hipStreamSynchronize(s));
@@ -255,10 +278,44 @@ int kzg_cells(ctt_eth_kzg_context_struct* c, uint8_t* cells, uint8_t* proofs, ui
     // 4. their evaluations over the domain of the Lagrange bases (bit-reversed, canonical: the MSM's coefficients), in place
     if (ctt_hip_fr_ntt(c->hip, c->ntt, c->d_cellq, c->d_cellq, N_CELLS, CTT_HIP_NTT_IN_MONT | CTT_HIP_NTT_OUT_BRP, nullptr) != 0) return GPU_UNAVAILABLE;
     ms[4] = ms_since(t0);
-    // 5. 128 MSMs over the cached bases, three tickets in flight (the header's advice for small MSMs)
     aff.resize((size_t)N_CELLS * 96);
+    // 5. the 128 MSMs in one pass over the table of the Lagrange points (built here the first time).  No memory for the table or its
+    // workspace, or a table that refuses its arguments: the loop below serves the call, now and from now on, so that no call is refused
+    // that the loop would have served; a failed HIP call is the GPU's.
+    bool by_table = false;
+    if (!c->proofs_loop) {
+      int rc = FX_OK;
+      if (!c->fixed) {
+        FixedTable* t = new FixedTable(c->device, s);
+        rc = t->build(FX_CURVE_BLS12_381_G1, c->lagrange_aff.data(), N_BLOB, c->proofs_c);
+        if (rc == FX_OK) {
+          c->fixed = t;
+          path[1] = t->build_ms();
+          std::vector<uint8_t>().swap(c->lagrange_aff);
+        } else {
+          if (rc == FX_HIP_ERROR) set_last_error(ERR_HIP_FAILURE, "cell proofs: %s", t->error());
+          delete t;
+        }
+      }
+      if (rc == FX_OK) {
+        rc = c->fixed->msm_batch(FX_COEF_BIG, c->d_cellq, N_CELLS, aff.data(), FX_COEFS_ON_DEVICE);
+        if (rc == FX_HIP_ERROR) set_last_error(ERR_HIP_FAILURE, "cell proofs: %s", c->fixed->error());
+      }
+      if (rc == FX_OUT_OF_MEMORY || rc == FX_REFUSED) {
+        c->proofs_loop = true;
+        delete c->fixed;
+        c->fixed = nullptr;
+        std::vector<uint8_t>().swap(c->lagrange_aff);
+      } else if (rc != FX_OK) {
+        return GPU_UNAVAILABLE;
+      } else {
+        by_table = true;
+        path[0] = (float)N_CELLS;
+      }
+    }
+    // ... or 128 MSMs over the cached bases, three tickets in flight (the header's advice for small MSMs)
     int ticket[N_CELLS];
-    int submitted = 0, finished = 0;
+    int submitted = 0, finished = by_table ? N_CELLS : 0;
     bool failed = false;
     while (!failed && finished < N_CELLS) {
       if (submitted < N_CELLS && submitted - finished < 3) {
@@ -289,6 +346,7 @@ int kzg_cells(ctt_eth_kzg_context_struct* c, uint8_t* cells, uint8_t* proofs, ui
   if (q_le) memcpy(q_le, q_host.data(), q_host.size());
   ms[6] = ms_since(t0);
   memcpy(c->cell_ms, ms, sizeof ms);
+  memcpy(c->cell_path, path, sizeof path);
   return KZG_Success;
 }
 
@@ -414,8 +472,9 @@ uint8_t ctt_eth_kzg_context_new(ctt_eth_kzg_context_struct** ctx, const char* fi
   return gpu_guarded([&]() { return kzg_context_build(ctx, srs.data(), dv ? atoi(dv) : 0, 1); });
 }
 // ethereum_eip4844_kzg.h:232: the reference's constructor with PrecomputedMSM lookup tables (t base groups, b bits per window -- CPU
-// tables for the FK20 proofs of PeerDAS).  The same context as above: the SRS is cached on the GPU as a window table whatever t and b
-// say; the cell proofs here are MSMs over that table, not FK20.
+// tables for the FK20 proofs of PeerDAS).  The same context as above whatever t and b say: the cell proofs here are not FK20 but 128
+// plain MSMs over the Lagrange points in one pass of the batched fixed-base MSM (fixed.h), whose precomputed table -- this library's
+// counterpart of those lookup tables, sized by $CTT_HIP_CELL_PROOFS_C -- is built at the first proof call.
 uint8_t ctt_eth_kzg_context_new_with_precompute(ctt_eth_kzg_context_struct** ctx, const char* filepath, uint8_t format, int /*t*/, int /*b*/) {
   return ctt_eth_kzg_context_new(ctx, filepath, format);
 }
@@ -504,14 +563,18 @@ uint8_t ctt_hip_eth_kzg_cell_quotients(const ctt_eth_kzg_context_struct* ctx, ui
   return cells_entry(ctx, nullptr, nullptr, q_le, blob);
 }
 // host-clock times (ms) of the context's last cells call, every step waited for: parse + upload, INTT, coset NTT, quotients,
-// batched NTT, MSM loop, compress + copy back.  Returns the number written.
+// batched NTT, the MSMs, compress + copy back; with cap >= 9 also [7] the rows of the cell proofs the table kernel served in that call
+// (128, or 0: the loop) and [8] the ms that call paid for building the table.  Returns the number written.
 int ctt_hip_eth_kzg_last_cell_timings(const ctt_eth_kzg_context_struct* ctx, float* ms, int cap) {
   if (!ctx || !ms) return -1;
   ctt_eth_kzg_context_struct* c = const_cast<ctt_eth_kzg_context_struct*>(ctx);
   std::lock_guard<std::mutex> lock(c->mu);
   const int n = cap < 7 ? cap : 7;
   for (int i = 0; i < n; i++) ms[i] = c->cell_ms[i];
-  return n;
+  if (cap < 9) return n;
+  ms[7] = c->cell_path[0];
+  ms[8] = c->cell_path[1];
+  return 9;
 }
 
 // the _parallel forms (ethereum_eip4844_kzg_parallel.h:40,61,73): the thread pool is not used, as in the MSM's _parallel symbols

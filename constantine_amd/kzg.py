@@ -182,6 +182,16 @@ def last_cell_timings(ctx: EthereumKZGContext):
     return list(ms)
 
 
+def last_cell_proof_path(ctx: EthereumKZGContext):
+    """-> ("table" | "loop", build_ms) of the context's last cells-and-proofs call: whether the batched fixed-base MSM served the 128
+    proofs in one pass or the loop over the cached SRS did (CTT_HIP_CELL_PROOFS=loop at creation, or no memory for the table), and
+    the ms that call paid for building the table (the first proof call of a context; 0 afterwards)"""
+    ms = (ctypes.c_float * 9)()
+    if ctx.L.ctt_hip_eth_kzg_last_cell_timings(ctx.handle, ms, 9) != 9:
+        raise RuntimeError("ctt_hip_eth_kzg_last_cell_timings: the library does not report the cell-proof path")
+    return ("table" if int(ms[7]) == CELLS_PER_EXT_BLOB else "loop"), float(ms[8])
+
+
 # the reference's _parallel forms (ethereum_eip4844_kzg_parallel.nim: `tp` first): the same GPU path, the thread pool is not used
 def blob_to_kzg_commitment_parallel(tp, ctx: EthereumKZGContext, blob: bytes) -> bytes:
     if len(blob) != BYTES_PER_BLOB:

@@ -384,7 +384,10 @@ typedef enum __attribute__((__packed__)) {
 /* the c-kzg text format of the Ethereum ceremony; the SRS is cached on $CTT_HIP_DEVICE (default 0) */
 ctt_eth_trusted_setup_status ctt_eth_kzg_context_new(ctt_eth_kzg_context** ctx, const char* filepath,
                                                      ctt_eth_trusted_setup_format format);
-/* ethereum_eip4844_kzg.h:232 -- t, b size the reference's CPU lookup tables (PeerDAS); accepted, the same context as above */
+/* ethereum_eip4844_kzg.h:232 -- t, b size the reference's CPU lookup tables (PeerDAS); accepted, the same context as above.  This
+ * library's counterpart of those tables is the table of the batched fixed-base MSM (include/ctt_msm_hip_fixed.h) that serves the 128
+ * cell proofs in one pass: every context builds it at its first proof call, whichever constructor made it; $CTT_HIP_CELL_PROOFS_C
+ * (window bits) sizes it, and $CTT_HIP_CELL_PROOFS=loop at creation keeps the loop of 128 MSMs over the cached SRS instead. */
 ctt_eth_trusted_setup_status ctt_eth_kzg_context_new_with_precompute(ctt_eth_kzg_context** ctx, const char* filepath,
                                                                      ctt_eth_trusted_setup_format format, int t, int b);
 void ctt_eth_kzg_context_delete(ctt_eth_kzg_context* ctx);
@@ -414,8 +417,9 @@ ctt_eth_kzg_status ctt_eth_kzg_compute_cells_and_kzg_proofs(const ctt_eth_kzg_co
 /* not in the reference's C header (its Nim API has compute_cells): the cells alone -- two transforms, no MSM */
 ctt_eth_kzg_status ctt_hip_eth_kzg_compute_cells(const ctt_eth_kzg_context* ctx, ctt_eth_kzg_cell cells[128], const ctt_eth_kzg_blob* blob);
 /* test-facing: the 128 x 4096 canonical little-endian coefficients of the cell quotients (the quotient kernel alone), and the
- * host-clock times (ms) of the context's last cells call: parse + upload, INTT, coset NTT, quotients, batched NTT, MSM loop,
- * compress + copy back (returns the number written) */
+ * host-clock times (ms) of the context's last cells call: parse + upload, INTT, coset NTT, quotients, batched NTT, the MSMs,
+ * compress + copy back; with cap >= 9 also [7] the rows of the cell proofs the table kernel served in that call (128, or 0: the
+ * loop) and [8] the ms that call paid for building the table (returns the number written: 9, or at most 7) */
 ctt_eth_kzg_status ctt_hip_eth_kzg_cell_quotients(const ctt_eth_kzg_context* ctx, uint8_t* q_le, const ctt_eth_kzg_blob* blob);
 int ctt_hip_eth_kzg_last_cell_timings(const ctt_eth_kzg_context* ctx, float* ms, int cap);
 ctt_evm_status ctt_eth_evm_bls12381_g1msm(ctt_byte* r, size_t r_len, const ctt_byte* inputs, size_t inputs_len);
