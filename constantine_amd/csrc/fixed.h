@@ -28,8 +28,9 @@ class FixedTable {
   // is checked before the first launch.  -> FX_OK, or a refusal code with error() set and no table.
   int build(int curve, const void* points_aff, size_t n, int c);
   // out_aff[k] = sum_i coefs[k][i] * P_i for k < m: coefs [m][n][32] (FX_COEF_BIG: canonical little-endian below 2^BITS, FX_COEF_FR:
-  // Montgomery residues of the scalar field), out_aff [m] affine points.  flags say which of the two are device pointers.  out_aff is
-  // written only on FX_OK.
+  // Montgomery residues of the scalar field), out_aff [m] affine points.  flags say which of the two are device pointers.  m * n * 32 below 2^31
+  // and m * ceil(n / 256) * 256 below 2^32 (one launch), checked before anything is reserved or launched.  out_aff is written only
+  // on FX_OK.
   int msm_batch(int coef_kind, const void* coefs, size_t m, void* out_aff, int flags);
 
   bool built() const { return tab_ != nullptr; }

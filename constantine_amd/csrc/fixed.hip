@@ -233,9 +233,15 @@ int FixedTable::msm_batch(int coef_kind, const void* coefs, size_t m, void* out_
   if (flags & ~(FX_COEFS_ON_DEVICE | FX_OUT_ON_DEVICE)) return fail(FX_REFUSED, "flags 0x%x", flags);
   if (m < 1 || m > (1ull << 26) || (uint64_t)m * n_ * 32u >= (1ull << 31))
     return fail(FX_REFUSED, "m = %zu rows of %zu scalars: 1 row or more, and m * n * 32 below 2^31", m, n_);
+  const uint32_t chunks = (uint32_t)((n_ + FX_BLOCK - 1) / FX_BLOCK);
+  // A launch has fewer than 2^32 work-items in x (the runtime refuses more as an invalid configuration): m * chunks blocks of FX_BLOCK
+  // lanes, and the finish's ceil(m / 4) blocks of 256.  With m * n * 32 below 2^31 only n <= 3 with m >= 2^24 is refused here.
+  const uint64_t sum_items = (uint64_t)m * chunks * FX_BLOCK;
+  const uint64_t finish_items = ((uint64_t)m + FX_FINISH_ROWS - 1) / FX_FINISH_ROWS * FX_FINISH_BLOCK;
+  if (sum_items >= (1ull << 32) || finish_items >= (1ull << 32))
+    return fail(FX_REFUSED, "m = %zu rows of %u chunks: m * chunks * %u below 2^32 (the work-items of one launch)", m, chunks, FX_BLOCK);
   FxDeviceScope scope(device_);
   if (!scope.ok) return fail(FX_HIP_ERROR, "device %d cannot be selected", device_);
-  const uint32_t chunks = (uint32_t)((n_ + FX_BLOCK - 1) / FX_BLOCK);
   const size_t coef_bytes = m * n_ * 32u, out_bytes = m * point_bytes();
   int rc;
   if ((rc = reserve(&part_, &part_bytes_, m * chunks * 2 * point_bytes())) != FX_OK) return rc;

@@ -35,8 +35,9 @@ void ctt_hip_fixed_bases_destroy(ctt_hip_fixed_bases* bases);
 int ctt_hip_fixed_bases_info(const ctt_hip_fixed_bases* bases, size_t info[6]);
 /* out_aff[k] = sum_i coefs[k][i] * P_i for k < m.  coefs: m rows of n scalars, row-major, 32 bytes each -- CTT_HIP_COEF_BIG: canonical
  * little-endian, any value below 2^255 (BN254: 2^254), not reduced mod r; CTT_HIP_COEF_FR: Montgomery residues of the scalar field.
- * out_aff: m affine points (x, y Montgomery), the neutral as (0, 0).  m >= 1 and m * n * 32 < 2^31.  flags: which of coefs and out_aff
- * are device pointers; the call returns when out_aff is written. */
+ * out_aff: m affine points (x, y Montgomery), the neutral as (0, 0).  m >= 1, m * n * 32 < 2^31 and m * ceil(n / 256) < 2^24 (one
+ * launch has fewer than 2^32 work-items; this only excludes n <= 3 with m >= 2^24): anything else is refused with -1.  flags: which of
+ * coefs and out_aff are device pointers; the call returns when out_aff is written. */
 int ctt_hip_fixed_msm_batch(ctt_hip_fixed_bases* bases, int coef_kind, const void* coefs, size_t m, void* out_aff, int flags);
 /* device times (ms) of the handle's last successful batch: the sum kernel, the finish */
 int ctt_hip_fixed_last_timings(const ctt_hip_fixed_bases* bases, float ms[2]);

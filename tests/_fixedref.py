@@ -69,6 +69,111 @@ def harness_msm_input(name, pts, coefs, c, fr=False):
     return struct.pack("<5I", CURVE_ID[name], n, c, 1 if fr else 0, m) + pts.tobytes() + coefs.tobytes()
 
 
+def rows_per_base(bits, c):
+    """records of one base: 2^(width - 1) per window"""
+    return sum(1 << (width - 1) for _, width in layout(bits, c))
+
+
+def booth_digits(k, lay):
+    """the signed digit of every window of `lay` for the scalar k (bigints.nim signedWindowEncoding over windows of their own width)"""
+    out = []
+    for off, width in lay:
+        d = ((k << 1) >> off) & ((1 << (width + 1)) - 1)
+        e = (d + 1) >> 1
+        out.append(e - (1 << width) if d >> width else e)
+    assert sum(dg << off for dg, (off, _) in zip(out, lay)) == k
+    return out
+
+
+def largest_digit_scalars(bits, c):
+    """three scalars below 2^bits with a digit of the largest magnitude 2^(width - 1) in the lowest window, in a middle window and in
+    the top window: -2^(width - 1), the top bit of the window alone (the window above takes the carry, +1), in the lowest and the
+    middle window; the top window has bit `bits` as its top bit, which no scalar sets, so its largest digit is +2^(width - 1): all its
+    other bits and the bit below it (the top bit of the window below, which so holds -2^(width - 1) too).  Each such digit reads the
+    last record of its window."""
+    lay = layout(bits, c)
+    W = len(lay)
+    out = []
+    for w in (0, W // 2):
+        off, width = lay[w]
+        k = 1 << (off + width - 1)
+        assert booth_digits(k, lay)[w] == -(1 << (width - 1))
+        out.append(k)
+    off, width = lay[W - 1]
+    k = ((1 << (width - 1)) - 1) << off | 1 << (off - 1)
+    assert k < 1 << bits and booth_digits(k, lay)[W - 1] == 1 << (width - 1)
+    out.append(k)
+    return out
+
+
+def harness_finish_input(name, part):
+    m, chunks = part.shape[:2]
+    return struct.pack("<3I", CURVE_ID[name], m, chunks) + part.tobytes()
+
+
+FINISH_CHUNKS = (1, 2, 63, 64, 65, 127, 128, 129, 192, 193, 255, 256)
+FINISH_ROWS = ("dense", "last only", "from 64 on", "all zero", "equal at s and s + 64", "opposite at s and s + 64")
+
+
+@functools.lru_cache(maxsize=None)
+def _finish_pool(name):
+    """(k_j, k_j * G) for 320 known k_j = k_0 + j * d, by running additions: two scalar multiplications in all"""
+    curve = po.CURVES[name]
+    rng = random.Random("finish pool " + name)
+    k0, d = rng.randrange(1, curve.order), rng.randrange(1, curve.order)
+    P, D = curve.scalar_mul(k0, curve.gen), curve.scalar_mul(d, curve.gen)
+    pool = []
+    for j in range(320):
+        pool.append(((k0 + j * d) % curve.order, P))
+        P = curve.add(P, D)
+    return pool
+
+
+def _xyzz_bytes(curve, P, z):
+    """(x z^2, y z^3, z^2, z^3) in Montgomery words; None: the in-memory neutral, all zero"""
+    F = curve.F
+    if P is None:
+        return bytes(4 * F.nbytes)
+    zz = F.sqr(z)
+    zzz = F.mul(zz, z)
+    return b"".join(F.to_mont_bytes(v) for v in (F.mul(P[0], zz), F.mul(P[1], zzz), zz, zzz))
+
+
+@functools.lru_cache(maxsize=None)
+def finish_case(name, chunks):
+    """-> (part (6, chunks, 4 * coordinate bytes) uint8, expect (6, aff) uint8): the six rows of FINISH_ROWS as XYZZ partials k * G
+    with known k, each with a random non-zero z of its own, and (sum of the row's k mod r) * G.  s, the lane of the last two rows, is
+    chunks - 65 where the row has a partial s + 64 (so at 256 chunks the pair is the third and fourth stride of lane 63), and the
+    pair is (0, chunks - 1) below 65 chunks."""
+    curve = po.CURVES[name]
+    pool = _finish_pool(name)
+    rng = random.Random(f"finish {name} {chunks}")
+    s0, s1 = (chunks - 65, chunks - 1) if chunks > 64 else (0, chunks - 1)
+    rows = []
+    for what in FINISH_ROWS:
+        row = [None] * chunks                                   # (k, point) per partial
+        if what == "dense":
+            row = [pool[rng.randrange(320)] for _ in range(chunks)]
+        elif what == "last only":
+            row[chunks - 1] = pool[rng.randrange(320)]
+        elif what == "from 64 on":
+            row = [pool[rng.randrange(320)] if s >= 64 else None for s in range(chunks)]
+        elif what == "equal at s and s + 64":                   # the rest of that lane's partials neutral: its sum so far is the point
+            row = [pool[rng.randrange(320)] if s % 64 != s0 % 64 else None for s in range(chunks)]
+            row[s0] = row[s1] = pool[rng.randrange(320)]
+        elif what == "opposite at s and s + 64":
+            k, P = pool[rng.randrange(320)]
+            row[s0] = (k, P)
+            if s1 != s0:
+                row[s1] = (curve.order - k, curve.neg(P))
+        rows.append(row)
+    part = b"".join(_xyzz_bytes(curve, e[1] if e else None, rng.randrange(1, curve.F.p)) for row in rows for e in row)
+    expect = [curve.scalar_mul(sum(e[0] for e in row if e) % curve.order, curve.gen) for row in rows]
+    if chunks > 1:
+        assert expect[3] is None and expect[5] is None
+    return (np.frombuffer(part, dtype=np.uint8).reshape(6, chunks, 4 * curve.F.nbytes).copy(), curve.points_to_array(expect))
+
+
 class Case:
     """name: the curve; pts (n, aff) uint8; coefs (m, n, 32) uint8 canonical; cs: the window sizes to run; expect (m, aff) uint8;
     coefs_fr: the same scalars mod r as Montgomery residues, where the case has that form"""
@@ -136,7 +241,21 @@ def case(tag):
         pts = cref.gen_points(bn, 24, 70)
         coefs = _scalars(curve, [[rng.getrandbits(254) for _ in range(70)] for _ in range(2)])
         return Case(bn, pts, coefs, (2, 8), _rows_by_cref(bn, pts, coefs))
+    if tag in ("T8", "T8bn"):   # the window sizes 7 and 9 .. 12 (and 2 on 255 bits): n = 5, six rows that hold every scalar edge once
+        name = bls if tag == "T8" else bn
+        curve = po.CURVES[name]
+        r, bits = curve.order, BITS[name]
+        cs = (2, 7, 9, 10, 11, 12) if tag == "T8" else (7, 9, 10, 11, 12)
+        rng = random.Random(tag)
+        pts = cref.gen_points(name, 25, 5)
+        edges = [0, 1, 2, r - 1, r, r + 1, 2**bits - 1] + [k for c in cs for k in largest_digit_scalars(bits, c)]
+        ks = edges + [rng.getrandbits(bits) for _ in range(-len(edges) % 5 + 5)]
+        rows = [ks[j:j + 5] for j in range(0, len(ks), 5)]
+        P = [curve.aff_from_bytes(bytes(p)) for p in pts]
+        expect = curve.points_to_array([curve.msm_naive(row, P) for row in rows])
+        fr = np.stack([curve.fr_scalars_to_array(row) for row in rows])
+        return Case(name, pts, _scalars(curve, rows), cs, expect, fr)
     raise KeyError(tag)
 
 
-MSM_CASES = ("T2", "T3", "T4", "T5", "T7")
+MSM_CASES = ("T2", "T3", "T4", "T5", "T7", "T8", "T8bn")

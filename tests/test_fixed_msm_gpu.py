@@ -24,7 +24,8 @@ def _torch():
 
 @pytest.mark.parametrize("tag", fx.MSM_CASES)
 def test_cases_with_host_arrays_and_with_device_tensors(tag):
-    """T2 scalar edges, T3 chunk edge (and T6: its Montgomery form), T4 collisions, T5 neutral and opposite bases, T7 BN254 G1"""
+    """T2 scalar edges, T3 chunk edge (and T6: its Montgomery form), T4 collisions, T5 neutral and opposite bases, T7 BN254 G1, T8 /
+    T8bn the scalar edges and the largest digits at c = 7, 9 .. 12 (and 2 on 255 bits), in both coefficient forms on both curves"""
     from constantine_amd import FixedBaseMsm
     torch = _torch()
     case = fx.case(tag)
