@@ -13,6 +13,7 @@ Only what the MSM hot path needs lives here:
   verkle.py  batched Verkle commitments over a fixed Banderwagon basis: VerkleCrs.commit, batchMapToScalarField, serializeBatch_vartime
   fixed.py  batched fixed-base MSM over BLS12-381 G1 / BN254 G1 (FixedBaseMsm; include/ctt_msm_hip_fixed.h -> libctt_msm_hip_fixed.so)
   ntt.py    batched NTT over a curve's scalar field (NttPlan); the EIP-7594 cells and cell proofs of kzg.py run on it
+  peerdas.py  EIP-7594 recovery batched over blobs (Recovery; include/ctt_msm_hip_peerdas.h -> libctt_msm_hip_peerdas.so)
   kzg.py, evm.py  ctypes callers of the reference's KZG / EIP-2537 MSM-precompile C symbols (csrc/protocols.hip: host side in C++)
 """
 from .curves import CURVES, CurveInfo  # noqa: F401

@@ -1,7 +1,7 @@
 """ctypes loader for libctt_msm_hip.so. The product path has no fallback: a missing library is an error.
 
-The prototypes of the libraries are the tables below, name -> (restype, argtypes); tests/test_abi_symbols.py and
-tests/test_fixed_abi.py derive the same from the C headers and compare."""
+The prototypes of the libraries are the tables below, name -> (restype, argtypes); tests/test_abi_symbols.py,
+tests/test_fixed_abi.py and tests/test_peerdas_recover_abi.py derive the same from the C headers and compare."""
 import ctypes
 import os
 
@@ -9,10 +9,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CTT_MSM_HIP_LIB") or os.path.join(HERE, "libctt_msm_hip.so")
 BW_LIB_PATH = os.path.join(HERE, "libctt_msm_hip_banderwagon.so")
 FIXED_LIB_PATH = os.path.join(HERE, "libctt_msm_hip_fixed.so")
+PEERDAS_LIB_PATH = os.path.join(HERE, "libctt_msm_hip_peerdas.so")
 
 _lib = None
 _bw_lib = None
 _fixed_lib = None
+_peerdas_lib = None
 ABI_VERSION = 11  # ctt_hip_msm_abi_version() of the library this package was written against
 GPU_UNAVAILABLE = 0xF0   # CTT_HIP_STATUS_GPU_UNAVAILABLE: what a protocol symbol returns when the GPU cannot serve the call
 
@@ -25,6 +27,7 @@ vp, sz, i32, u32, u64, cstr = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ct
 u8 = ctypes.c_uint8                                  # the reference's status enums are __attribute__((__packed__)): one byte
 pvp, pi32 = ctypes.POINTER(vp), ctypes.POINTER(i32)  # out-handles and int arrays the callers pass with byref / as ctypes arrays
 psz, pf32 = ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_float)
+pu64 = ctypes.POINTER(u64)
 
 
 def _msm_families():
@@ -137,6 +140,19 @@ FIXED_PROTOTYPES = {
 }
 
 
+# include/ctt_msm_hip_peerdas.h: EIP-7594 recovery, batched over blobs (a library with kernels of its own over the C ABI of lib())
+PEERDAS_PROTOTYPES = {
+    "ctt_hip_peerdas_recovery_create": (vp, [i32]),
+    "ctt_hip_peerdas_recovery_destroy": (None, [vp]),
+    "ctt_hip_peerdas_recover_blobs": (i32, [vp, vp, vp, pu64, vp, sz, sz]),
+    "ctt_hip_eth_kzg_recover_cells_and_kzg_proofs_batch": (u8, [vp, vp, vp, vp, pu64, vp, sz, sz]),
+    "ctt_eth_kzg_recover_cells_and_kzg_proofs": (u8, [vp, vp, vp, pu64, vp, sz]),
+    "ctt_hip_peerdas_recover_coefficients": (i32, [vp, vp, vp, pu64, vp, sz, sz]),
+    "ctt_hip_peerdas_recovery_constants": (i32, [vp, vp, pu64, sz]),
+    "ctt_hip_peerdas_last_timings": (i32, [vp, pf32, i32]),
+}
+
+
 def exported_symbols():
     """Every symbol include/ctt_msm_hip.h declares."""
     return list(PROTOTYPES)
@@ -208,6 +224,17 @@ def fixed_lib():
         _share_hip_runtime_with_torch()
         _fixed_lib = _load(FIXED_LIB_PATH, FIXED_PROTOTYPES, "ctt_msm_hip_fixed.h")
     return _fixed_lib
+
+
+def peerdas_lib():
+    """libctt_msm_hip_peerdas.so (include/ctt_msm_hip_peerdas.h): EIP-7594 recovery, over lib()."""
+    global _peerdas_lib
+    if _peerdas_lib is None:
+        lib()   # the engine first: the companion library resolves against the copy already loaded
+        if not os.path.exists(PEERDAS_LIB_PATH):
+            raise HipLibraryMissing(f"{PEERDAS_LIB_PATH} not found: build it with make -C constantine_amd/csrc")
+        _peerdas_lib = _load(PEERDAS_LIB_PATH, PEERDAS_PROTOTYPES, "ctt_msm_hip_peerdas.h")
+    return _peerdas_lib
 
 
 def lib():

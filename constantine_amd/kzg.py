@@ -19,7 +19,11 @@ EIP-7594 (PeerDAS) on the same context:
     ctt_hip_eth_kzg_compute_cells              the cells alone (the reference's Nim API has it, its C header does not)
 
 The blob's coefficients, the coset evaluations of the cells and the evaluations of the 128 cell quotients are transforms of the
-scalar-field NTT (ntt.py); the proofs are 128 MSMs over the cached Lagrange SRS.  recover_cells_and_kzg_proofs,
+scalar-field NTT (ntt.py); the proofs are 128 MSMs over the cached Lagrange SRS.
+
+    ctt_eth_kzg_recover_cells_and_kzg_proofs   the same header, :91 -- in the companion library libctt_msm_hip_peerdas.so
+                                               (peerdas.py has the batched form)
+
 verify_cell_kzg_proof_batch (pairings) and the FK20 form of the proofs are out of scope.
 """
 import ctypes
@@ -164,6 +168,21 @@ def compute_cells_and_kzg_proofs(ctx: EthereumKZGContext, blob: bytes):
     raw, pr = bytes(cells), bytes(proofs)
     return ([raw[BYTES_PER_CELL * k:BYTES_PER_CELL * (k + 1)] for k in range(CELLS_PER_EXT_BLOB)],
             [pr[48 * k:48 * (k + 1)] for k in range(CELLS_PER_EXT_BLOB)])
+
+
+def recover_cells_and_kzg_proofs(ctx: EthereumKZGContext, cell_indices, cells):
+    """-> (128 cells of 2048 bytes, 128 proofs of 48 bytes) of the blob that at least 64 of its cells determine:
+    ctt_eth_kzg_recover_cells_and_kzg_proofs (libctt_msm_hip_peerdas.so).  cells: len(cell_indices) byte strings of 2048; a count or a
+    length that does not fit is a ValueError, what the reference rejects a KzgError with its status."""
+    from . import peerdas
+    idx, arr, batched = peerdas.pack_cells(cell_indices, cells)
+    if batched:
+        raise ValueError("one blob's cells: a batch goes through peerdas.Recovery")
+    out_c = np.zeros((CELLS_PER_EXT_BLOB, BYTES_PER_CELL), dtype=np.uint8)
+    out_p = np.zeros((CELLS_PER_EXT_BLOB, 48), dtype=np.uint8)
+    _check(_lib.peerdas_lib().ctt_eth_kzg_recover_cells_and_kzg_proofs(ctx.handle, ptr(out_c), ptr(out_p), idx.ctypes.data_as(_lib.pu64),
+                                                                       ptr(arr), idx.shape[0]))
+    return [out_c[k].tobytes() for k in range(CELLS_PER_EXT_BLOB)], [out_p[k].tobytes() for k in range(CELLS_PER_EXT_BLOB)]
 
 
 def cell_quotients(ctx: EthereumKZGContext, blob: bytes) -> np.ndarray:

@@ -353,7 +353,7 @@ void* ctt_hip_msm_stream(ctt_hip_msm_ctx* ctx);
  * (constantine_amd/csrc/protocols.hip), MSMs / subgroup checks / quotient polynomial on the GPU.  Verification (pairings) and the
  * other precompiles are out of scope and not exported.  EIP-7594 (PeerDAS): compute_cells_and_kzg_proofs of
  *   include/constantine/protocols/ethereum_eip7594_peerdas.h
- * and the cells alone; recover_cells_and_kzg_proofs, verify_cell_kzg_proof_batch and the FK20 form are out of scope.  There is no CPU fallback, and none of
+ * and the cells alone (recover_cells_and_kzg_proofs: ctt_msm_hip_peerdas.h); verify_cell_kzg_proof_batch and the FK20 form are out of scope.  There is no CPU fallback, and none of
  * these symbols terminates the process (round 5; rounds 1-4 aborted): a call the GPU cannot serve -- no device, out of device
  * memory, a failed HIP call -- returns CTT_HIP_STATUS_GPU_UNAVAILABLE, a value outside every status enum below (the reference's
  * *_status_to_string print "InvalidStatusCode" for it), leaves its outputs untouched, and ctt_hip_last_error() of the calling
