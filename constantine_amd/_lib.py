@@ -1,7 +1,7 @@
 """ctypes loader for libctt_msm_hip.so. The product path has no fallback: a missing library is an error.
 
 The prototypes of the libraries are the tables below, name -> (restype, argtypes); tests/test_abi_symbols.py,
-tests/test_fixed_abi.py and tests/test_peerdas_recover_abi.py derive the same from the C headers and compare."""
+tests/test_fixed_abi.py, tests/test_peerdas_recover_abi.py and tests/test_peerdas_verify_abi.py derive the same from the C headers and compare."""
 import ctypes
 import os
 
@@ -10,11 +10,13 @@ LIB_PATH = os.environ.get("CTT_MSM_HIP_LIB") or os.path.join(HERE, "libctt_msm_h
 BW_LIB_PATH = os.path.join(HERE, "libctt_msm_hip_banderwagon.so")
 FIXED_LIB_PATH = os.path.join(HERE, "libctt_msm_hip_fixed.so")
 PEERDAS_LIB_PATH = os.path.join(HERE, "libctt_msm_hip_peerdas.so")
+VERIFY_LIB_PATH = os.path.join(HERE, "libctt_msm_hip_peerdas_verify.so")
 
 _lib = None
 _bw_lib = None
 _fixed_lib = None
 _peerdas_lib = None
+_verify_lib = None
 ABI_VERSION = 11  # ctt_hip_msm_abi_version() of the library this package was written against
 GPU_UNAVAILABLE = 0xF0   # CTT_HIP_STATUS_GPU_UNAVAILABLE: what a protocol symbol returns when the GPU cannot serve the call
 
@@ -153,6 +155,20 @@ PEERDAS_PROTOTYPES = {
 }
 
 
+# include/ctt_msm_hip_peerdas_verify.h: EIP-7594 batch verification (a library with kernels of its own and the host pairing, over the C
+# ABI of lib())
+VERIFY_PROTOTYPES = {
+    "ctt_hip_peerdas_verifier_create": (vp, [i32, vp, vp]),
+    "ctt_hip_peerdas_verifier_create_from_file": (vp, [i32, cstr]),
+    "ctt_hip_peerdas_verifier_destroy": (None, [vp]),
+    "ctt_hip_peerdas_verify_cell_kzg_proof_batch": (i32, [vp, vp, pu64, vp, vp, sz, vp]),
+    "ctt_hip_peerdas_verify_challenge": (i32, [vp, vp, sz, pu64, pu64, vp, vp, sz]),
+    "ctt_hip_peerdas_verify_lincombs": (i32, [vp, vp, vp, vp, vp, pu64, vp, vp, sz, vp]),
+    "ctt_hip_peerdas_pairing_check": (i32, [vp, vp, sz]),
+    "ctt_hip_peerdas_verify_last_timings": (i32, [vp, pf32, i32]),
+}
+
+
 def exported_symbols():
     """Every symbol include/ctt_msm_hip.h declares."""
     return list(PROTOTYPES)
@@ -235,6 +251,17 @@ def peerdas_lib():
             raise HipLibraryMissing(f"{PEERDAS_LIB_PATH} not found: build it with make -C constantine_amd/csrc")
         _peerdas_lib = _load(PEERDAS_LIB_PATH, PEERDAS_PROTOTYPES, "ctt_msm_hip_peerdas.h")
     return _peerdas_lib
+
+
+def verify_lib():
+    """libctt_msm_hip_peerdas_verify.so (include/ctt_msm_hip_peerdas_verify.h): EIP-7594 batch verification, over lib()."""
+    global _verify_lib
+    if _verify_lib is None:
+        lib()   # the engine first: the companion library resolves against the copy already loaded
+        if not os.path.exists(VERIFY_LIB_PATH):
+            raise HipLibraryMissing(f"{VERIFY_LIB_PATH} not found: build it with make -C constantine_amd/csrc")
+        _verify_lib = _load(VERIFY_LIB_PATH, VERIFY_PROTOTYPES, "ctt_msm_hip_peerdas_verify.h")
+    return _verify_lib
 
 
 def lib():

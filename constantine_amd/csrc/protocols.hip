@@ -10,7 +10,8 @@
 // the Fiat-Shamir hash, point (de)compression, the trusted setup's text reader, the precompiles' parser and encoder; this file reads
 // no wire-format byte itself.  GPU side, here: the KZG context, every MSM (cached SRS: ctt_hip_msm_with_bases; precompile inputs:
 // ctt_hip_msm_host), the subgroup checks (ctt_hip_subgroup_check) and the quotient polynomial of an opening (ctt_hip_fr_quotient; the
-// branch "z is a root of unity" runs the reference's other formula on the host).  Verification needs pairings: out of scope.
+// branch "z is a root of unity" runs the reference's other formula on the host).  The EIP-4844 verifications are not provided; the EIP-7594 batch
+// verification, with its one pairing check on the host, is the companion library of verify.hip.
 //
 //   EIP-7594 PeerDAS ctt_eth_kzg_compute_cells_and_kzg_proofs (include/constantine/protocols/ethereum_eip7594_peerdas.h) and the
 //                   cells alone (ctt_hip_eth_kzg_compute_cells): the blob's coefficients, the coset evaluations and the 128 cell

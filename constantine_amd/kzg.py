@@ -10,8 +10,8 @@ constantine_amd/csrc/protocols.hip):
 
 Wire parsing, range checks, the Fiat-Shamir hash and point (de)compression are C++ on the host, every MSM, the subgroup check
 and the quotient polynomial run on the GPU.  Nothing is computed in Python here; the only checks this module adds are the byte
-LENGTHS, which the C signatures fix by type (ctt_eth_kzg_blob = 131072 bytes ...) and a Python `bytes` does not.  Verification
-needs pairings and is out of scope.
+LENGTHS, which the C signatures fix by type (ctt_eth_kzg_blob = 131072 bytes ...) and a Python `bytes` does not.  The EIP-4844
+verifications (verify_kzg_proof, verify_blob_kzg_proof*) are not provided.
 
 EIP-7594 (PeerDAS) on the same context:
 
@@ -24,7 +24,9 @@ scalar-field NTT (ntt.py); the proofs are 128 MSMs over th
     ctt_eth_kzg_recover_cells_and_kzg_proofs   the same header, :91 -- in the companion library libctt_msm_hip_peerdas.so
                                                (peerdas.py has the batched form)
 
-verify_cell_kzg_proof_batch (pairings) and the FK20 form of the proofs are out of scope.
+verify_cell_kzg_proof_batch is peerdas.Verifier: a companion library of its own, libctt_msm_hip_peerdas_verify.so, whose verifier object
+owns the monomial points the check needs; the device does what grows with the batch, the host the one pairing check (DESIGN.md
+section 16).  The FK20 form of the proofs is out of scope.
 """
 import ctypes
 from enum import Enum
